@@ -370,7 +370,7 @@ __global__ void k_to_internal(i64 n, const i64 *__restrict__ gids, i64 base,
 // a remote one is lnv + its index in the sorted rc_ids array (indexes
 // rc_info/rcu directly). The per-edge community gather halves to 4 B and
 // the gain scan's per-candidate binary search disappears; only the
-// tie-break needs label ORDER, fetched lazily (see k4_sweep_p1's note).
+// tie-break needs label ORDER, fetched lazily (see the K4 note).
 __global__ void k_build_view(i64 n, const i64 *__restrict__ labels, i64 base,
                              i64 bound, i64 lnv,
                              const unsigned *__restrict__ sigma_inv,
@@ -546,6 +546,26 @@ __global__ void k_depermute(i64 lnv, const unsigned *__restrict__ sigma_inv,
         out[v] = in[sigma_inv[v]];
 }
 
+// ---- Single-rank (p==1) u32 SLOT community arrays (the encoding is
+// described in the K4 note below): init and trace de-permute ----
+__global__ void k3_init_comm32(i64 lnv, unsigned *__restrict__ curr,
+                               unsigned *__restrict__ past) {
+    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < lnv;
+         k += (i64)gridDim.x * blockDim.x) {
+        curr[k] = (unsigned)k; // slot k's own community (dspl.hpp:132-149)
+        past[k] = (unsigned)k;
+    }
+}
+
+__global__ void k_depermute32(i64 lnv, const unsigned *__restrict__ sigma,
+                              const unsigned *__restrict__ sigma_inv,
+                              const unsigned *__restrict__ in,
+                              i64 *__restrict__ out) {
+    for (i64 v = blockIdx.x * (i64)blockDim.x + threadIdx.x; v < lnv;
+         v += (i64)gridDim.x * blockDim.x)
+        out[v] = (i64)sigma[in[sigma_inv[v]]]; // slot -> label
+}
+
 // ---- K4: THE sweep (distExecuteLouvainIteration, dspl.hpp:276-405) ----
 // One lane per vertex over the SELL image (see the layout note at the top).
 // The clmap/counter hash (dspl.hpp:230-274) lives as per-lane slot arrays:
@@ -554,15 +574,209 @@ __global__ void k_depermute(i64 lnv, const unsigned *__restrict__ sigma_inv,
 // (only populated while communities are still fine-grained; L2-resident).
 // The current community's accumulator is a register (the reference's
 // counter[0], dspl.hpp:312-318).
-// ---- K4 multi-rank sweep over the u32 VIEW (see k_build_view) ----
-// Same structure as k4_sweep_p1: per-lane LDS slot arrays + spill, edges
-// in chunks of 8, lazy tie-break labels. A community value < lnv is a
-// local internal slot (cinfo/cupd index); >= lnv is lnv + rc index
-// (rc_info/rcu index). Labels for the tie-break / singleton guard come
-// from sigma (+base) or rc_ids, fetched only on gain ties (dspl.hpp:
-// 174-228 order semantics preserved bit-for-bit).
-template <int SLOTS, bool UNIT>
-__global__ __launch_bounds__(256) void k4_sweep_mr(
+//
+// Community encoding. Every sweep runs over a u32 VIEW (see k_build_view):
+// a value < lnv is a local internal slot (cinfo/cupd index), a value >= lnv
+// is lnv + rc index (rc_info/rcu index). Equality probes only need
+// community identity and the info lookups need exactly this index, so the
+// per-edge community gather (the sweep's dominant random traffic) is 4 B
+// with NO added indirection on the info lookups. Only the reference's
+// tie-break and singleton guard need label ORDER (dspl.hpp:214-225), and
+// only per DISTINCT candidate: labels come from sigma (+base) or rc_ids,
+// fetched lazily — only when a gain tie actually needs the order — so the
+// common strict-greater path costs no label traffic at all (dspl.hpp:
+// 174-228 order semantics preserved bit-for-bit). (A pure-label variant
+// was measured and rejected: sigma_inv[label]->cinfo adds a dependent-load
+// chain to the latency-bound gain scan — 4M 104G vs 110G handles vs this
+// design.)
+//
+// Mode (template parameter MR). MR=true is the multi-rank VIEW mode above.
+// MR=false is single-rank SLOT mode: the view without ghosts. At one rank
+// every community is local and base is 0, so the persistent u32 slot
+// arrays ARE the view, a label is sigma[slot] (u32), and every remote
+// branch folds away at compile time — the ghost/rc pointers are passed
+// (1-element dummies) but never read.
+//
+// Shapes: k4_sweep (the general LDS-slot sweep), k4_sweep_iter1 (streaming
+// first iteration), k4_sweep_hi (wave-per-vertex hubs) and k4_sweep_lh
+// (lane-hash band; view form at every rank count). They share the
+// fragments below, each written once.
+
+// label type: i64 global ids in view mode, the u32 sigma value in slot mode
+template <bool MR> using label_t = std::conditional_t<MR, i64, unsigned>;
+
+// label of an owned internal slot
+template <bool MR>
+__device__ __forceinline__ label_t<MR> own_label(i64 v, i64 base,
+                                                 const unsigned *sigma) {
+    if constexpr (MR) return base + (i64)sigma[v];
+    else return sigma[v];
+}
+
+// label of a view value (tie-break / singleton-guard order only,
+// dspl.hpp:214-225). clamp0: the un-taken rc_ids side must stay
+// dereferenceable when the select is if-converted (see clamp0).
+template <bool MR>
+__device__ __forceinline__ label_t<MR> label_of(unsigned v, i64 lnv, i64 base,
+                                                const unsigned *sigma,
+                                                const i64 *rc_ids) {
+    if constexpr (MR)
+        return (v < lnv) ? own_label<MR>(v, base, sigma)
+                         : rc_ids[clamp0(v - lnv)];
+    else return sigma[v];
+}
+
+// community {size, degree}: localCinfo, or the fetched remote record
+// (dspl.hpp:296-307)
+template <bool MR>
+__device__ __forceinline__ Cinfo comm_info(unsigned v, i64 lnv,
+                                           const Cinfo *cinfo,
+                                           const Info16 *rc_info) {
+    if (!MR || v < lnv) return cinfo[v];
+    const Info16 c = rc_info[v - lnv];
+    return {c.size, c.degree};
+}
+
+// one side of a move: (dsize, ddeg) onto localCupdate / remoteCupdate
+template <bool MR>
+__device__ __forceinline__ void comm_add(unsigned c, i64 dsize, double ddeg,
+                                         i64 lnv, Cinfo *cupd, Info16 *rcu) {
+    if (!MR || c < lnv) {
+        Cinfo *u = &cupd[c];
+        atomicAdd(&u->degree, ddeg);
+        atomic_add_i64(&u->size, dsize);
+    } else {
+        Info16 *u = &rcu[c - lnv];
+        atomicAdd(&u->degree, ddeg);
+        atomic_add_i64(&u->size, dsize);
+    }
+}
+
+// the 4-case move update (dspl.hpp:331-399); SRC_MR / DST_MR: whether that
+// side can be remote (at iteration 1 the source is always local)
+template <bool SRC_MR, bool DST_MR>
+__device__ __forceinline__ void move_update(unsigned from, unsigned to,
+                                            double vdeg, i64 lnv, Cinfo *cupd,
+                                            Info16 *rcu) {
+    comm_add<SRC_MR>(from, -1, -vdeg, lnv, cupd, rcu);
+    comm_add<DST_MR>(to, 1, vdeg, lnv, cupd, rcu);
+}
+
+// Edges go in chunks of CH: issue the CH independent tail loads and the CH
+// dependent gathers together (the per-edge serial load->gather->probe chain
+// was the measured bound: 80% SQ_WAIT_ANY with LDS and VALU idle), then
+// consume sequentially in edge order (bit-exact -w accumulation,
+// dspl.hpp:240-271). Steps past the row end re-load the row's first slot.
+constexpr int CH = 8;
+
+template <bool UNIT>
+__device__ __forceinline__ void load_tails(i64 ebase, int k0, int m,
+                                           const int *sell_tidx,
+                                           const double *sell_w,
+                                           i64 (&tb)[CH], double (&wb)[CH]) {
+#pragma unroll
+    for (int j = 0; j < CH; j++) {
+        const i64 slot = (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
+        tb[j] = sell_tidx[slot];
+        if (!UNIT) wb[j] = sell_w[slot];
+    }
+}
+
+// tails (+ weights unless UNIT) and their communities
+template <bool MR, bool UNIT>
+__device__ __forceinline__ void load_chunk(i64 ebase, int k0, int m, i64 lnv,
+                                           const int *sell_tidx,
+                                           const double *sell_w,
+                                           const unsigned *vcurr,
+                                           const unsigned *vghost,
+                                           i64 (&tb)[CH], double (&wb)[CH],
+                                           unsigned (&cb)[CH]) {
+    load_tails<UNIT>(ebase, k0, m, sell_tidx, sell_w, tb, wb);
+#pragma unroll
+    for (int j = 0; j < CH; j++)
+        cb[j] = (!MR || tb[j] < lnv) ? vcurr[tb[j]]
+                                     : vghost[clamp0(tb[j] - lnv)];
+}
+
+// dQ gain (dspl.hpp:212) — operand order and parenthesisation are the
+// reference's; with -ffp-contract=off this carries its exact bits
+__device__ __forceinline__ double dq_gain(double eiy, double eix, double vdeg,
+                                          double ay, double ax,
+                                          double constant) {
+    return 2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
+}
+
+// first probe position in a power-of-two open-addressed region (Fibonacci)
+__device__ __forceinline__ i64 hash_start(unsigned tcomm, i64 cap) {
+    return (i64)(((uint64_t)tcomm * 0x9E3779B97F4A7C15ull) >> 32) & (cap - 1);
+}
+
+// distGetMaxIndex, lane form (dspl.hpp:174-228), one candidate (y, eiy):
+// strict-greater gain, gain ties to the smaller label (:214-215). With the
+// label tie-break the argmax is a total order, so any scan order gives the
+// reference's answer. The scan loop stays in the calling kernel (as one
+// helper with a candidate functor it cost the view-mode sweep an
+// occupancy step: 74 VGPRs instead of 72).
+template <bool MR>
+__device__ __forceinline__ void argmax_step(
+    unsigned y, double eiy, double eix, double vdeg, double ax,
+    double constant, i64 lnv, i64 base, const unsigned *sigma,
+    const Cinfo *cinfo, const i64 *rc_ids, const Info16 *rc_info,
+    double &maxGain, unsigned &maxIndex, i64 &maxSize) {
+    const Cinfo c = comm_info<MR>(y, lnv, cinfo, rc_info);
+    const double curGain = dq_gain(eiy, eix, vdeg, c.degree, ax, constant);
+    if (curGain > maxGain) {
+        maxGain = curGain;
+        maxIndex = y;
+        maxSize = c.size;
+    } else if (curGain == maxGain && curGain != 0.0) {
+        // real branch, not a select: the label loads must not be folded
+        // into the gain-compare dataflow (ROCm 7.2 if-conversion
+        // miscompile)
+        if (label_of<MR>(y, lnv, base, sigma, rc_ids) <
+            label_of<MR>(maxIndex, lnv, base, sigma, rc_ids)) {
+            maxIndex = y;
+            maxSize = c.size;
+        }
+    }
+}
+
+// ... and the singleton guard that closes the scan (dspl.hpp:224-225)
+template <bool MR>
+__device__ __forceinline__ unsigned singleton_guard(
+    unsigned maxIndex, i64 maxSize, unsigned cc, i64 ccSize, i64 lnv,
+    i64 base, const unsigned *sigma, const i64 *rc_ids) {
+    if (maxSize == 1 && ccSize == 1 && maxIndex != cc) {
+        if (label_of<MR>(maxIndex, lnv, base, sigma, rc_ids) >
+            label_of<MR>(cc, lnv, base, sigma, rc_ids))
+            maxIndex = cc;
+    }
+    return maxIndex;
+}
+
+// distGetMaxIndex, wave form: each lane holds its best candidate as (gain
+// bg, packed bl = label << 32 | view, community size bs); reduce to lane 0
+// under the total order (gain desc, bl asc) — label order decides and the
+// view rides along for free; order-independent, so the reduce tree
+// reproduces dspl.hpp:214-215 exactly. A lane without a positive-gain
+// candidate holds the neutral element (0.0, INT64_MAX) and can never win.
+__device__ __forceinline__ void wave_reduce_best(double &bg, i64 &bl,
+                                                 i64 &bs) {
+    for (int off = 32; off > 0; off >>= 1) {
+        const double og = __shfl_down(bg, off, 64);
+        const i64 ol = __shfl_down(bl, off, 64);
+        const i64 os = __shfl_down(bs, off, 64);
+        if (og > bg || (og == bg && ol < bl)) {
+            bg = og;
+            bl = ol;
+            bs = os;
+        }
+    }
+}
+
+// ---- K4 general sweep: LDS slots + spill, any iteration ----
+template <bool MR, int SLOTS, bool UNIT>
+__global__ __launch_bounds__(256) void k4_sweep(
     i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
@@ -585,27 +799,12 @@ __global__ __launch_bounds__(256) void k4_sweep_mr(
     unsigned *myspill_k = spill_keys + spill_off[gthread];
     double *myspill_a = spill_acc + spill_off[gthread];
 
-    // lazy label fetch (tie-break order only, dspl.hpp:214-225)
-    auto label_of = [&](unsigned v) -> i64 {
-        return (v < lnv) ? base + (i64)sigma[v] : rc_ids[clamp0(v - lnv)];
-    };
-
     for (i64 s = s_begin + gthread; s < s_end; s += stride) {
         const i64 i = perm[s];          // internal vertex index
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
         const unsigned cc = vcurr[i];
-        double ccDeg;
-        i64 ccSize;
-        if (cc < lnv) { // dspl.hpp:296-307
-            const Cinfo c = cinfo[cc];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        } else {
-            const Info16 c = rc_info[cc - lnv];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        }
+        const Cinfo cci = comm_info<MR>(cc, lnv, cinfo, rc_info);
         unsigned target;
         if (deg == 0) {
             target = cc;          // dspl.hpp:323-324
@@ -613,28 +812,13 @@ __global__ __launch_bounds__(256) void k4_sweep_mr(
         } else {
             double c0 = 0.0, selfLoop = 0.0;
             int ns = 0, nspill = 0;
-            // Edges in chunks of 8: issue the 8 independent tail loads and
-            // the 8 dependent community gathers together (the per-edge
-            // serial load->gather->probe chain was the measured bound: 80%
-            // SQ_WAIT_ANY with LDS and VALU idle), then probe sequentially
-            // in edge order (bit-exact -w accumulation, dspl.hpp:240-271).
-            constexpr int CH = 8;
             for (int k0 = 0; k0 < deg; k0 += CH) {
                 const int m = min(CH, deg - k0);
                 i64 tb[CH];
                 unsigned cb[CH];
                 double wb[CH];
-#pragma unroll
-                for (int j = 0; j < CH; j++) {
-                    const i64 slot =
-                        (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
-                    tb[j] = sell_tidx[slot];
-                    if (!UNIT) wb[j] = sell_w[slot];
-                }
-#pragma unroll
-                for (int j = 0; j < CH; j++)
-                    cb[j] = (tb[j] < lnv) ? vcurr[tb[j]]
-                                          : vghost[clamp0(tb[j] - lnv)];
+                load_chunk<MR, UNIT>(ebase, k0, m, lnv, sell_tidx, sell_w,
+                                     vcurr, vghost, tb, wb, cb);
                 for (int j = 0; j < m; j++) {
                     const i64 tidx = tb[j];
                     const double w = UNIT ? 1.0 : wb[j];
@@ -672,88 +856,45 @@ __global__ __launch_bounds__(256) void k4_sweep_mr(
             }
             clusterWeight[i] = c0; // dspl.hpp:318 onto the K5-zeroed value
 
-            // distGetMaxIndex (dspl.hpp:174-228); labels fetched lazily
+            // distGetMaxIndex: LDS slots first, then the spill in
+            // insertion order
             const double vdeg = vDegree[i];
             const double eix = c0 - selfLoop;
-            const double ax = ccDeg - vdeg;
+            const double ax = cci.degree - vdeg;
             double maxGain = 0.0;
             unsigned maxIndex = cc;
-            i64 maxSize = ccSize;
+            i64 maxSize = cci.size;
             const int tot = ns + nspill;
             for (int t = 0; t < tot; t++) {
                 const unsigned y = (t < ns) ? skey[t * blockDim.x + tid]
                                             : myspill_k[t - ns];
                 const double eiy = (t < ns) ? sacc[t * blockDim.x + tid]
                                             : myspill_a[t - ns];
-                double ay;
-                i64 ysz;
-                if (y < lnv) {
-                    const Cinfo c = cinfo[y];
-                    ay = c.degree;
-                    ysz = c.size;
-                } else {
-                    const Info16 c = rc_info[y - lnv];
-                    ay = c.degree;
-                    ysz = c.size;
-                }
-                const double curGain =
-                    2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant; // :212
-                if (curGain > maxGain) {
-                    maxGain = curGain;
-                    maxIndex = y;
-                    maxSize = ysz;
-                } else if (curGain == maxGain && curGain != 0.0) {
-                    // real branch, not a select: the label loads must not
-                    // be folded into the gain-compare dataflow (ROCm 7.2
-                    // if-conversion miscompile)
-                    if (label_of(y) < label_of(maxIndex)) {
-                        maxIndex = y;
-                        maxSize = ysz;
-                    }
-                }
+                argmax_step<MR>(y, eiy, eix, vdeg, ax, constant, lnv, base,
+                                sigma, cinfo, rc_ids, rc_info, maxGain,
+                                maxIndex, maxSize);
             }
-            if (maxSize == 1 && ccSize == 1 && maxIndex != cc) { // :224-225
-                if (label_of(maxIndex) > label_of(cc)) maxIndex = cc;
-            }
-            target = maxIndex;
+            target = singleton_guard<MR>(maxIndex, maxSize, cc, cci.size, lnv,
+                                         base, sigma, rc_ids);
         }
 
-        if (target != cc) { // 4-case updates (dspl.hpp:331-399)
-            const double vdeg = vDegree[i];
-            if (cc < lnv) {
-                Cinfo *u = &cupd[cc];
-                atomicAdd(&u->degree, -vdeg);
-                atomic_add_i64(&u->size, -1);
-            } else {
-                Info16 *u = &rcu[cc - lnv];
-                atomicAdd(&u->degree, -vdeg);
-                atomic_add_i64(&u->size, -1);
-            }
-            if (target < lnv) {
-                Cinfo *u = &cupd[target];
-                atomicAdd(&u->degree, vdeg);
-                atomic_add_i64(&u->size, 1);
-            } else {
-                Info16 *u = &rcu[target - lnv];
-                atomicAdd(&u->degree, vdeg);
-                atomic_add_i64(&u->size, 1);
-            }
-        }
+        if (target != cc)
+            move_update<MR, MR>(cc, target, vDegree[i], lnv, cupd, rcu);
         vtarget[i] = target; // dspl.hpp:404 (view; persisted as a label)
     }
 }
 
-// ---- K4 high-degree path (wave-per-vertex), multi-rank VIEW mode ----
+// ---- K4 high-degree path (wave-per-vertex) ----
 // For skewed graphs (Orkut-class hubs), one WAVE processes one vertex:
 // lanes stride the CSR row (coalesced 8-B tails), aggregate into a
 // per-vertex open-addressed hash in HBM (L2-resident; u32 view keys CASed
 // from ~0, weights atomicAdd), then a wave-reduce argmax applies the
-// reference tie-break as a total order on (gain, label<<32|view) — order-
-// independent, so the reduce tree reproduces dspl.hpp:214-215 exactly.
-// Unit-weight graphs only: their sums are integer-exact under any
-// accumulation order; -w skewed graphs take the serial lane path instead
-// (edge-order bit parity).
-__global__ __launch_bounds__(256) void k4_sweep_hi_mr(
+// reference tie-break (wave_reduce_best). Unit-weight graphs only: their sums are integer-exact under
+// any accumulation order; -w skewed graphs take the serial lane path
+// instead (edge-order bit parity). tidx32 holds pre-translated internal
+// indices (at p==1 a global tail id IS the local vertex id).
+template <bool MR>
+__global__ __launch_bounds__(256) void k4_sweep_hi(
     i64 nhi, i64 lnv, i64 base, const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const unsigned *__restrict__ sigma,
     const i64 *__restrict__ xadj, const int *__restrict__ tidx32,
@@ -767,9 +908,6 @@ __global__ __launch_bounds__(256) void k4_sweep_hi_mr(
     const int lane = threadIdx.x & 63;
     const int wid = threadIdx.x >> 6;
     const int wpb = blockDim.x >> 6;
-    auto label_of = [&](unsigned v) -> i64 {
-        return (v < lnv) ? base + (i64)sigma[v] : rc_ids[clamp0(v - lnv)];
-    };
     for (i64 s = (i64)blockIdx.x * wpb + wid; s < nhi;
          s += (i64)gridDim.x * wpb) {
         const i64 i = perm[s];
@@ -779,27 +917,16 @@ __global__ __launch_bounds__(256) void k4_sweep_hi_mr(
         const unsigned cc = vcurr[i];
         const i64 hoff = hash_off[s];
         const i64 cap = hash_off[s + 1] - hoff; // power of two
-        double ccDeg;
-        i64 ccSize;
-        if (cc < lnv) {
-            const Cinfo c = cinfo[cc];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        } else {
-            const Info16 c = rc_info[cc - lnv];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        }
+        const Cinfo cci = comm_info<MR>(cc, lnv, cinfo, rc_info);
         double c0 = 0.0, selfLoop = 0.0;
         for (int k = lane; k < deg; k += 64) {
             const i64 ti = tidx32[e0 + k]; // pre-translated internal index
             const double w = 1.0;          // hub path is unit-only
             if (ti == i) selfLoop += w;
-            const unsigned tcomm = (ti < lnv) ? vcurr[ti]
-                                              : vghost[ti - lnv];
+            const unsigned tcomm = (!MR || ti < lnv) ? vcurr[ti]
+                                                     : vghost[ti - lnv];
             if (tcomm == cc) { c0 += w; continue; }
-            i64 pos = (i64)(((uint64_t)tcomm * 0x9E3779B97F4A7C15ull) >> 32) &
-                      (cap - 1);
+            i64 pos = hash_start(tcomm, cap);
             for (;;) {
                 const i64 prev = (i64)atomicCAS(
                     (unsigned long long *)&hkeys[hoff + pos],
@@ -820,53 +947,35 @@ __global__ __launch_bounds__(256) void k4_sweep_hi_mr(
         selfLoop = __shfl(selfLoop, 0, 64);
         const double vdeg = vDegree[i];
         const double eix = c0 - selfLoop;
-        const double ax = ccDeg - vdeg;
-        // per-lane best over hash slots, then wave-reduce under the total
-        // order (gain desc, (label, view) asc); gain <= 0 maps to the
-        // neutral element so it can never win (dspl.hpp:214-215)
+        const double ax = cci.degree - vdeg;
+        // per-lane best over the hash slots, then the wave reduce
         double bg = 0.0;
-        i64 bl = INT64_MAX, bs = 0; // bl = (label << 32) | view
+        i64 bl = INT64_MAX, bs = 0;
         for (i64 t = lane; t < cap; t += 64) {
             const i64 yk = hkeys[hoff + t];
             if (yk == -1) continue;
             const unsigned y = (unsigned)yk;
             const double eiy = hacc[hoff + t];
-            double ay;
-            i64 ysz;
-            if (y < lnv) {
-                const Cinfo c = cinfo[y];
-                ay = c.degree;
-                ysz = c.size;
-            } else {
-                const Info16 c = rc_info[y - lnv];
-                ay = c.degree;
-                ysz = c.size;
-            }
-            const double g =
-                2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
-            const i64 yh = (label_of(y) << 32) | (i64)y;
+            const Cinfo c = comm_info<MR>(y, lnv, cinfo, rc_info);
+            const double g = dq_gain(eiy, eix, vdeg, c.degree, ax, constant);
+            const i64 yh =
+                ((i64)label_of<MR>(y, lnv, base, sigma, rc_ids) << 32) |
+                (i64)y;
             if (g > bg || (g == bg && g != 0.0 && yh < bl)) {
                 bg = g;
                 bl = yh;
-                bs = ysz;
+                bs = c.size;
             }
         }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double og = __shfl_down(bg, off, 64);
-            const i64 ol = __shfl_down(bl, off, 64);
-            const i64 os = __shfl_down(bs, off, 64);
-            if (og > bg || (og == bg && ol < bl)) {
-                bg = og;
-                bl = ol;
-                bs = os;
-            }
-        }
+        wave_reduce_best(bg, bl, bs);
         if (lane == 0) {
+            const label_t<MR> ccLabel =
+                label_of<MR>(cc, lnv, base, sigma, rc_ids);
             unsigned target =
                 (bl == INT64_MAX) ? cc : (unsigned)(bl & 0xffffffffu);
-            const i64 tLabel =
-                (bl == INT64_MAX) ? label_of(cc) : (bl >> 32);
-            if (bs == 1 && ccSize == 1 && tLabel > label_of(cc))
+            const label_t<MR> tLabel =
+                (bl == INT64_MAX) ? ccLabel : (label_t<MR>)(bl >> 32);
+            if (bs == 1 && cci.size == 1 && tLabel > ccLabel)
                 target = cc; // :224-225
             if (deg == 0) {
                 clusterWeight[i] = 0;
@@ -874,26 +983,8 @@ __global__ __launch_bounds__(256) void k4_sweep_hi_mr(
             } else {
                 clusterWeight[i] = c0;
             }
-            if (target != cc) {
-                if (cc < lnv) {
-                    Cinfo *u = &cupd[cc];
-                    atomicAdd(&u->degree, -vdeg);
-                    atomic_add_i64(&u->size, -1);
-                } else {
-                    Info16 *u = &rcu[cc - lnv];
-                    atomicAdd(&u->degree, -vdeg);
-                    atomic_add_i64(&u->size, -1);
-                }
-                if (target < lnv) {
-                    Cinfo *u = &cupd[target];
-                    atomicAdd(&u->degree, vdeg);
-                    atomic_add_i64(&u->size, 1);
-                } else {
-                    Info16 *u = &rcu[target - lnv];
-                    atomicAdd(&u->degree, vdeg);
-                    atomic_add_i64(&u->size, 1);
-                }
-            }
+            if (target != cc)
+                move_update<MR, MR>(cc, target, vdeg, lnv, cupd, rcu);
             vtarget[i] = target;
         }
     }
@@ -904,11 +995,11 @@ __global__ __launch_bounds__(256) void k4_sweep_hi_mr(
 // -w (dspl.hpp:240-271) — with the clmap as an open-addressed per-VERTEX
 // hash (d_hash_off regions) PLUS a compact candidate list (d_lh_list):
 // O(1) expected insert/lookup instead of the LDS path's O(ncand) linear
-// probe per edge, and the argmax scans exactly ncand entries instead of
-// the whole hash capacity. This is the aggregation structure for
-// vertices whose persistent distinct-candidate count exceeds the LDS
-// slots (long-range-edge-heavy social graphs). Works for p==1 too: the
-// u32 slot array IS the view there (base 0, no ghosts).
+// probe per edge, and the argmax scans exactly ncand entries (in insertion
+// order) instead of the whole hash capacity. This is the aggregation
+// structure for vertices whose persistent distinct-candidate count exceeds
+// the LDS slots (long-range-edge-heavy social graphs). One view-form
+// instantiation per UNIT serves p==1 too (the slot array IS the view).
 template <bool UNIT>
 __global__ __launch_bounds__(256) void k4_sweep_lh(
     i64 s_begin, i64 s_end, i64 lnv, i64 base,
@@ -923,11 +1014,9 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
     unsigned *__restrict__ vtarget, double *__restrict__ clusterWeight,
     const i64 *__restrict__ hash_off, i64 *__restrict__ hkeys,
     double *__restrict__ hacc, unsigned *__restrict__ lh_list) {
+    constexpr bool MR = true;
     const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    auto label_of = [&](unsigned v) -> i64 {
-        return (v < lnv) ? base + (i64)sigma[v] : rc_ids[clamp0(v - lnv)];
-    };
     for (i64 s = s_begin + gthread; s < s_end; s += stride) {
         const i64 i = perm[s];
         const int deg = (int)deg_int[i];
@@ -936,42 +1025,22 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
         const i64 hoff = hash_off[s];
         const i64 cap = hash_off[s + 1] - hoff; // power of two
         unsigned *mylist = lh_list + (hoff >> 1); // cap/2 >= deg entries
-        double ccDeg;
-        i64 ccSize;
-        if (cc < lnv) {
-            const Cinfo c = cinfo[cc];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        } else {
-            const Info16 c = rc_info[cc - lnv];
-            ccDeg = c.degree;
-            ccSize = c.size;
-        }
+        const Cinfo cci = comm_info<MR>(cc, lnv, cinfo, rc_info);
         double c0 = 0.0, selfLoop = 0.0;
         int ncand = 0;
-        constexpr int CH = 8;
         for (int k0 = 0; k0 < deg; k0 += CH) {
             const int m = min(CH, deg - k0);
             i64 tb[CH];
             unsigned cb[CH];
             double wb[CH];
-#pragma unroll
-            for (int j = 0; j < CH; j++) {
-                const i64 slot = (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
-                tb[j] = sell_tidx[slot];
-                if (!UNIT) wb[j] = sell_w[slot];
-            }
-#pragma unroll
-            for (int j = 0; j < CH; j++)
-                cb[j] = (tb[j] < lnv) ? vcurr[tb[j]]
-                                      : vghost[clamp0(tb[j] - lnv)];
+            load_chunk<MR, UNIT>(ebase, k0, m, lnv, sell_tidx, sell_w, vcurr,
+                                 vghost, tb, wb, cb);
             for (int j = 0; j < m; j++) {
                 const double w = UNIT ? 1.0 : wb[j];
                 if (tb[j] == i) selfLoop += w; // dspl.hpp:247-248
                 const unsigned tcomm = cb[j];
                 if (tcomm == cc) { c0 += w; continue; }
-                i64 pos = (i64)(((uint64_t)tcomm * 0x9E3779B97F4A7C15ull)
-                                >> 32) & (cap - 1);
+                i64 pos = hash_start(tcomm, cap);
                 for (;;) {
                     const i64 key = hkeys[hoff + pos];
                     if (key == (i64)tcomm) {
@@ -990,69 +1059,25 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
         }
         clusterWeight[i] = c0; // dspl.hpp:318
 
-        // distGetMaxIndex over the compact list (dspl.hpp:174-228); the
-        // scan order is insertion order — fine: the argmax with the lazy
-        // label tie-break is a total order, order-independent.
+        // distGetMaxIndex over the compact list
         const double vdeg = vDegree[i];
         const double eix = c0 - selfLoop;
-        const double ax = ccDeg - vdeg;
+        const double ax = cci.degree - vdeg;
         double maxGain = 0.0;
         unsigned maxIndex = cc;
-        i64 maxSize = ccSize;
+        i64 maxSize = cci.size;
         for (int t = 0; t < ncand; t++) {
             const i64 pos = mylist[t];
-            const unsigned y = (unsigned)hkeys[hoff + pos];
-            const double eiy = hacc[hoff + pos];
-            double ay;
-            i64 ysz;
-            if (y < lnv) {
-                const Cinfo c = cinfo[y];
-                ay = c.degree;
-                ysz = c.size;
-            } else {
-                const Info16 c = rc_info[y - lnv];
-                ay = c.degree;
-                ysz = c.size;
-            }
-            const double curGain =
-                2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
-            if (curGain > maxGain) {
-                maxGain = curGain;
-                maxIndex = y;
-                maxSize = ysz;
-            } else if (curGain == maxGain && curGain != 0.0) {
-                // real branch, not a select (DESIGN.md §4 miscompile note)
-                if (label_of(y) < label_of(maxIndex)) {
-                    maxIndex = y;
-                    maxSize = ysz;
-                }
-            }
+            argmax_step<MR>((unsigned)hkeys[hoff + pos], hacc[hoff + pos],
+                            eix, vdeg, ax, constant, lnv, base, sigma, cinfo,
+                            rc_ids, rc_info, maxGain, maxIndex, maxSize);
         }
-        if (maxSize == 1 && ccSize == 1 && maxIndex != cc) { // :224-225
-            if (label_of(maxIndex) > label_of(cc)) maxIndex = cc;
-        }
-        if (deg == 0) maxIndex = cc;
-        if (maxIndex != cc) {
-            if (cc < lnv) {
-                Cinfo *u = &cupd[cc];
-                atomicAdd(&u->degree, -vdeg);
-                atomic_add_i64(&u->size, -1);
-            } else {
-                Info16 *u = &rcu[cc - lnv];
-                atomicAdd(&u->degree, -vdeg);
-                atomic_add_i64(&u->size, -1);
-            }
-            if (maxIndex < lnv) {
-                Cinfo *u = &cupd[maxIndex];
-                atomicAdd(&u->degree, vdeg);
-                atomic_add_i64(&u->size, 1);
-            } else {
-                Info16 *u = &rcu[maxIndex - lnv];
-                atomicAdd(&u->degree, vdeg);
-                atomic_add_i64(&u->size, 1);
-            }
-        }
-        vtarget[i] = maxIndex;
+        unsigned target = singleton_guard<MR>(maxIndex, maxSize, cc, cci.size,
+                                              lnv, base, sigma, rc_ids);
+        if (deg == 0) target = cc;
+        if (target != cc)
+            move_update<MR, MR>(cc, target, vdeg, lnv, cupd, rcu);
+        vtarget[i] = target;
     }
 }
 
@@ -1061,27 +1086,25 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
 // counter[0] collects exactly the self-loop weight (eix = counter[0] -
 // selfLoop == 0.0, dspl.hpp:183), ax = ccDegree - vDegree == 0.0 (:185),
 // every community has size 1, and each distinct neighbor TAIL is its own
-// candidate. With per-row tails sorted ascending (the reference CSR's
-// order, graph.hpp:1145-1153 — verified at load), parallel edges are
-// adjacent and candidates arrive in ascending label order, so the
-// tie-break (max gain, then smallest label, dspl.hpp:214-215) reduces to a
-// strict-greater streaming argmax: no clmap at all, and the candidate's
-// degree ay is vDegree[tidx] — a spatially local gather instead of a
-// random cinfo line. The singleton guard (dspl.hpp:224-225) is the final
-// maxIndex > cc check. Gains carry the identical bits: 2.0*(eiy-0.0) and
-// (ay-0.0) round exactly like the reference's expressions.
-// Multi-rank iteration-1 streaming specialization, VIEW mode (see
-// k4_sweep_iter1_p1's header note). currComm is the identity, so a LOCAL
-// candidate's view is its tail index and its ay is vDegree[tidx]; a ghost
-// candidate's view comes from vghost (already lnv + rc index — the old
-// per-edge rc binary search disappears). Labels for the final singleton
-// guard come batched from sigma / the sorted ghost id list.
+// candidate — no community gather at all. With per-row tails sorted
+// ascending (the reference CSR's order, graph.hpp:1145-1153 — verified at
+// load), parallel edges are adjacent and candidates arrive in ascending
+// label order, so the tie-break (max gain, then smallest label,
+// dspl.hpp:214-215) reduces to a strict-greater streaming argmax: no clmap
+// at all. A LOCAL candidate's view is its tail index and its degree ay is
+// vDegree[tidx] — a spatially local gather instead of a random cinfo line;
+// a ghost candidate's view comes from vghost (already lnv + rc index — the
+// old per-edge rc binary search disappears). The singleton guard
+// (dspl.hpp:224-225) is the final maxLabel > ccLabel check, on labels that
+// come batched from sigma / the sorted ghost id list. Gains carry the
+// identical bits: dq_gain with eix = ax = 0.0 rounds exactly like the
+// reference's expressions (x - 0.0 == x).
 // LBL_ASC: rows are label-ascending (the reference CSR order), so the
 // strict-greater argmax implicitly keeps the smallest label on gain ties.
 // With internal-sorted rows (k_sell_sort_rows) candidates stream in
 // INTERNAL order instead and ties compare the batched labels explicitly.
-template <bool UNIT, bool LBL_ASC>
-__global__ __launch_bounds__(256) void k4_sweep_iter1_mr(
+template <bool MR, bool UNIT, bool LBL_ASC>
+__global__ __launch_bounds__(256) void k4_sweep_iter1(
     i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
@@ -1092,6 +1115,7 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1_mr(
     const Info16 *__restrict__ rc_info, Info16 *__restrict__ rcu,
     double constant, unsigned *__restrict__ vtarget,
     double *__restrict__ clusterWeight) {
+    using label = label_t<MR>;
     const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     const i64 stride = (i64)gridDim.x * blockDim.x;
     for (i64 s = s_begin + gthread; s < s_end; s += stride) {
@@ -1099,54 +1123,50 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1_mr(
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
         const unsigned cc = (unsigned)i; // own slot (identity)
-        const i64 ccLabel = base + (i64)sigma[i];
+        const label ccLabel = own_label<MR>(i, base, sigma);
         const double vdeg = vDegree[i];
         double c0 = 0.0;
         double maxGain = 0.0;
         unsigned maxIndex = cc;
-        i64 maxLabel = ccLabel;
+        label maxLabel = ccLabel;
         i64 prev = INT64_MIN;
         unsigned pend_view = 0;
-        i64 pend_label = 0;
+        label pend_label = 0;
         double eiy = 0.0, pend_ay = 0.0;
         bool pend = false;
-        constexpr int CH = 8;
+        auto close_pending = [&] { // the pending candidate is complete
+            const double g = dq_gain(eiy, 0.0, vdeg, pend_ay, 0.0, constant);
+            if (g > maxGain) {
+                maxGain = g;
+                maxIndex = pend_view;
+                maxLabel = pend_label;
+            } else if (!LBL_ASC && g == maxGain && g != 0.0 &&
+                       pend_label < maxLabel) {
+                maxIndex = pend_view; // dspl.hpp:214-215 tie
+                maxLabel = pend_label;
+            }
+        };
         for (int k0 = 0; k0 < deg; k0 += CH) {
             const int m = min(CH, deg - k0);
-            i64 tb[CH], lb[CH];
+            i64 tb[CH];
+            label lb[CH];
             double wb[CH], vb[CH];
+            load_tails<UNIT>(ebase, k0, m, sell_tidx, sell_w, tb, wb);
 #pragma unroll
             for (int j = 0; j < CH; j++) {
-                const i64 slot = (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
-                tb[j] = sell_tidx[slot];
-                if (!UNIT) wb[j] = sell_w[slot];
-            }
-#pragma unroll
-            for (int j = 0; j < CH; j++) {
-                lb[j] = (tb[j] < lnv) ? base + (i64)sigma[tb[j]]
-                                      : ghosts[clamp0(tb[j] - lnv)];
-                vb[j] = (tb[j] < lnv) ? vDegree[tb[j]] : 0.0;
+                const bool local = !MR || tb[j] < lnv;
+                lb[j] = local ? own_label<MR>(tb[j], base, sigma)
+                              : (label)ghosts[clamp0(tb[j] - lnv)];
+                vb[j] = local ? vDegree[tb[j]] : 0.0;
             }
             for (int j = 0; j < m; j++) {
                 const i64 tidx = tb[j];
                 const double w = UNIT ? 1.0 : wb[j];
                 if (tidx == i) { c0 += w; continue; } // self: counter[0]
                 if (tidx == prev) { eiy += w; continue; } // parallel edge
-                if (pend) {
-                    const double g =
-                        2.0 * eiy - 2.0 * vdeg * pend_ay * constant;
-                    if (g > maxGain) {
-                        maxGain = g;
-                        maxIndex = pend_view;
-                        maxLabel = pend_label;
-                    } else if (!LBL_ASC && g == maxGain && g != 0.0 &&
-                               pend_label < maxLabel) {
-                        maxIndex = pend_view; // dspl.hpp:214-215 tie
-                        maxLabel = pend_label;
-                    }
-                }
+                if (pend) close_pending();
                 prev = tidx;
-                if (tidx < lnv) {
+                if (!MR || tidx < lnv) {
                     pend_view = (unsigned)tidx; // candidate comm == tail
                     pend_ay = vb[j];
                 } else {
@@ -1158,418 +1178,12 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1_mr(
                 pend = true;
             }
         }
-        if (pend) {
-            const double g = 2.0 * eiy - 2.0 * vdeg * pend_ay * constant;
-            if (g > maxGain) {
-                maxGain = g;
-                maxIndex = pend_view;
-                maxLabel = pend_label;
-            } else if (!LBL_ASC && g == maxGain && g != 0.0 &&
-                       pend_label < maxLabel) {
-                maxIndex = pend_view;
-                maxLabel = pend_label;
-            }
-        }
+        if (pend) close_pending();
         if (maxLabel > ccLabel) maxIndex = cc; // singleton guard
         clusterWeight[i] = c0;                 // dspl.hpp:318 (eix == 0)
-        if (maxIndex != cc) {                  // cc is local at iteration 1
-            Cinfo *u = &cupd[i];
-            atomicAdd(&u->degree, -vdeg);
-            atomic_add_i64(&u->size, -1);
-            if (maxIndex < lnv) {
-                Cinfo *t = &cupd[maxIndex];
-                atomicAdd(&t->degree, vdeg);
-                atomic_add_i64(&t->size, 1);
-            } else {
-                Info16 *t = &rcu[maxIndex - lnv];
-                atomicAdd(&t->degree, vdeg);
-                atomic_add_i64(&t->size, 1);
-            }
-        }
+        if (maxIndex != cc)                    // cc is local at iteration 1
+            move_update<false, MR>(cc, maxIndex, vdeg, lnv, cupd, rcu);
         vtarget[i] = maxIndex;
-    }
-}
-
-
-// ---- Single-rank (p==1) specializations: u32 SLOT communities ----
-// At one rank every community is local (base 0, no ghosts, no remote
-// paths), so a community value can be the 32-bit internal SLOT of its
-// home vertex: equality probes only need community identity, and
-// cinfo/cupd indexing needs exactly the slot — so the per-edge community
-// gather (the sweep's dominant random traffic) halves to 4 B with NO
-// added indirection on the info lookups. Only the reference's tie-break
-// and singleton guard need label ORDER (dspl.hpp:214-225), and only per
-// DISTINCT candidate: the label is sigma[slot], an independent
-// spatially-clustered gather. (A pure-label variant was measured and
-// rejected: sigma_inv[label]->cinfo adds a dependent-load chain to the
-// latency-bound gain scan — 4M 104G vs 110G handles vs this design.)
-__global__ void k3_init_comm32(i64 lnv, unsigned *__restrict__ curr,
-                               unsigned *__restrict__ past) {
-    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < lnv;
-         k += (i64)gridDim.x * blockDim.x) {
-        curr[k] = (unsigned)k; // slot k's own community (dspl.hpp:132-149)
-        past[k] = (unsigned)k;
-    }
-}
-
-__global__ void k_depermute32(i64 lnv, const unsigned *__restrict__ sigma,
-                              const unsigned *__restrict__ sigma_inv,
-                              const unsigned *__restrict__ in,
-                              i64 *__restrict__ out) {
-    for (i64 v = blockIdx.x * (i64)blockDim.x + threadIdx.x; v < lnv;
-         v += (i64)gridDim.x * blockDim.x)
-        out[v] = (i64)sigma[in[sigma_inv[v]]]; // slot -> label
-}
-
-template <int SLOTS, bool UNIT>
-__global__ __launch_bounds__(256) void k4_sweep_p1(
-    i64 s_begin, i64 lnv, const unsigned *__restrict__ perm,
-    const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
-    const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
-    const unsigned *__restrict__ currComm,
-    const double *__restrict__ vDegree, const unsigned *__restrict__ sigma,
-    const Cinfo *__restrict__ cinfo, Cinfo *__restrict__ cupd,
-    double constant, unsigned *__restrict__ targetComm,
-    double *__restrict__ clusterWeight, unsigned *__restrict__ spill_keys,
-    double *__restrict__ spill_acc, const i64 *__restrict__ spill_off) {
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    double *sacc = reinterpret_cast<double *>(smem);
-    unsigned *skey = reinterpret_cast<unsigned *>(
-        smem + sizeof(double) * SLOTS * blockDim.x);
-    const int tid = threadIdx.x;
-    const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    unsigned *myspill_k = spill_keys + spill_off[gthread];
-    double *myspill_a = spill_acc + spill_off[gthread];
-
-    for (i64 s = s_begin + gthread; s < lnv; s += stride) {
-        const i64 i = perm[s];          // internal vertex index
-        const int deg = (int)deg_int[i];
-        const i64 ebase = chunk_off[s >> 6] + (s & 63);
-        const unsigned cc = currComm[i]; // slot
-        const Cinfo ci = cinfo[cc];
-        const double ccDeg = ci.degree;
-        const i64 ccSize = ci.size;
-        unsigned target;
-        if (deg == 0) {
-            target = cc;          // dspl.hpp:323-324
-            clusterWeight[i] = 0; // K5 semantics (dspl.hpp:481-482)
-        } else {
-            double c0 = 0.0, selfLoop = 0.0;
-            int ns = 0, nspill = 0;
-            constexpr int CH = 8;
-            for (int k0 = 0; k0 < deg; k0 += CH) {
-                const int m = min(CH, deg - k0);
-                i64 tb[CH];
-                unsigned cb[CH];
-                double wb[CH];
-#pragma unroll
-                for (int j = 0; j < CH; j++) {
-                    const i64 slot =
-                        (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
-                    tb[j] = sell_tidx[slot];
-                    if (!UNIT) wb[j] = sell_w[slot];
-                }
-#pragma unroll
-                for (int j = 0; j < CH; j++) cb[j] = currComm[tb[j]];
-                for (int j = 0; j < m; j++) {
-                    const i64 tidx = tb[j];
-                    const double w = UNIT ? 1.0 : wb[j];
-                    if (tidx == i) selfLoop += w; // dspl.hpp:247-248
-                    const unsigned tcomm = cb[j];
-                    if (tcomm == cc) { c0 += w; continue; }
-                    bool found = false;
-                    for (int t = 0; t < ns; t++) {
-                        if (skey[t * blockDim.x + tid] == tcomm) {
-                            sacc[t * blockDim.x + tid] += w;
-                            found = true;
-                            break;
-                        }
-                    }
-                    if (found) continue;
-                    if (ns < SLOTS) {
-                        skey[ns * blockDim.x + tid] = tcomm;
-                        sacc[ns * blockDim.x + tid] = w;
-                        ns++;
-                        continue;
-                    }
-                    for (int t = 0; t < nspill; t++) {
-                        if (myspill_k[t] == tcomm) {
-                            myspill_a[t] += w;
-                            found = true;
-                            break;
-                        }
-                    }
-                    if (!found) {
-                        myspill_k[nspill] = tcomm;
-                        myspill_a[nspill] = w;
-                        nspill++;
-                    }
-                }
-            }
-            clusterWeight[i] = c0; // dspl.hpp:318
-
-            // distGetMaxIndex (dspl.hpp:174-228); order on LABELS, but
-            // labels (sigma[slot]) are fetched LAZILY — only when a gain
-            // tie actually needs the order — so the common strict-greater
-            // path costs no label traffic at all.
-            const double vdeg = vDegree[i];
-            const double eix = c0 - selfLoop;
-            const double ax = ccDeg - vdeg;
-            double maxGain = 0.0;
-            unsigned maxIndex = cc;
-            i64 maxSize = ccSize;
-            const int tot = ns + nspill;
-            for (int t = 0; t < tot; t++) {
-                const unsigned y = (t < ns) ? skey[t * blockDim.x + tid]
-                                            : myspill_k[t - ns];
-                const double eiy = (t < ns) ? sacc[t * blockDim.x + tid]
-                                            : myspill_a[t - ns];
-                const Cinfo c = cinfo[y];
-                const double ay = c.degree;
-                const i64 ysz = c.size;
-                const double curGain =
-                    2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant; // :212
-                if (curGain > maxGain) {
-                    maxGain = curGain;
-                    maxIndex = y;
-                    maxSize = ysz;
-                } else if (curGain == maxGain && curGain != 0.0) {
-                    // real branch, not a select: the label loads must not
-                    // be folded into the gain-compare dataflow
-                    if (sigma[y] < sigma[maxIndex]) {
-                        maxIndex = y;
-                        maxSize = ysz;
-                    }
-                }
-            }
-            if (maxSize == 1 && ccSize == 1 && maxIndex != cc) { // :224-225
-                if (sigma[maxIndex] > sigma[cc]) maxIndex = cc;
-            }
-            target = maxIndex;
-        }
-
-        if (target != cc) { // both communities local (dspl.hpp:331-399)
-            const double vdeg = vDegree[i];
-            Cinfo *u = &cupd[cc];
-            atomicAdd(&u->degree, -vdeg);
-            atomic_add_i64(&u->size, -1);
-            Cinfo *t = &cupd[target];
-            atomicAdd(&t->degree, vdeg);
-            atomic_add_i64(&t->size, 1);
-        }
-        targetComm[i] = target; // dspl.hpp:404 (slot)
-    }
-}
-
-// iteration-1 streaming specialization, slot mode (see k4_sweep_iter1's
-// header note). currComm is the identity permutation, so a candidate
-// community IS its tail index — no community gather at all; the
-// label-order stream property and ay = vDegree[tidx] carry over.
-template <bool UNIT, bool LBL_ASC>
-__global__ __launch_bounds__(256) void k4_sweep_iter1_p1(
-    i64 s_begin, i64 lnv, const unsigned *__restrict__ perm,
-    const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
-    const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
-    const double *__restrict__ vDegree, const unsigned *__restrict__ sigma,
-    Cinfo *__restrict__ cupd, double constant,
-    unsigned *__restrict__ targetComm, double *__restrict__ clusterWeight) {
-    const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 s = s_begin + gthread; s < lnv; s += stride) {
-        const i64 i = perm[s];
-        const int deg = (int)deg_int[i];
-        const i64 ebase = chunk_off[s >> 6] + (s & 63);
-        const unsigned cc = (unsigned)i; // own slot
-        const unsigned ccLabel = sigma[i];
-        const double vdeg = vDegree[i];
-        double c0 = 0.0;
-        double maxGain = 0.0;
-        unsigned maxIndex = cc;
-        unsigned maxLabel = ccLabel;
-        i64 prev = INT64_MIN;
-        unsigned pend_slot = 0, pend_label = 0;
-        double eiy = 0.0, pend_ay = 0.0;
-        bool pend = false;
-        constexpr int CH = 8;
-        for (int k0 = 0; k0 < deg; k0 += CH) {
-            const int m = min(CH, deg - k0);
-            i64 tb[CH];
-            unsigned lb[CH];
-            double wb[CH], vb[CH];
-#pragma unroll
-            for (int j = 0; j < CH; j++) {
-                const i64 slot = (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
-                tb[j] = sell_tidx[slot];
-                if (!UNIT) wb[j] = sell_w[slot];
-            }
-#pragma unroll
-            for (int j = 0; j < CH; j++) {
-                lb[j] = sigma[tb[j]];
-                vb[j] = vDegree[tb[j]];
-            }
-            for (int j = 0; j < m; j++) {
-                const i64 tidx = tb[j];
-                const double w = UNIT ? 1.0 : wb[j];
-                if (tidx == i) { c0 += w; continue; } // self: counter[0]
-                if (tidx == prev) { eiy += w; continue; } // parallel edge
-                if (pend) {
-                    const double g =
-                        2.0 * eiy - 2.0 * vdeg * pend_ay * constant;
-                    if (g > maxGain) {
-                        maxGain = g;
-                        maxIndex = pend_slot;
-                        maxLabel = pend_label;
-                    } else if (!LBL_ASC && g == maxGain && g != 0.0 &&
-                               pend_label < maxLabel) {
-                        maxIndex = pend_slot; // dspl.hpp:214-215 tie
-                        maxLabel = pend_label;
-                    }
-                }
-                prev = tidx;
-                pend_slot = (unsigned)tidx; // candidate community == tail
-                pend_label = lb[j];
-                eiy = w;
-                pend_ay = vb[j];
-                pend = true;
-            }
-        }
-        if (pend) {
-            const double g = 2.0 * eiy - 2.0 * vdeg * pend_ay * constant;
-            if (g > maxGain) {
-                maxGain = g;
-                maxIndex = pend_slot;
-                maxLabel = pend_label;
-            } else if (!LBL_ASC && g == maxGain && g != 0.0 &&
-                       pend_label < maxLabel) {
-                maxIndex = pend_slot;
-                maxLabel = pend_label;
-            }
-        }
-        if (maxLabel > ccLabel) maxIndex = cc; // singleton guard
-        clusterWeight[i] = c0;                 // dspl.hpp:318 (eix == 0)
-        if (maxIndex != cc) {
-            Cinfo *u = &cupd[i];
-            atomicAdd(&u->degree, -vdeg);
-            atomic_add_i64(&u->size, -1);
-            Cinfo *t = &cupd[maxIndex];
-            atomicAdd(&t->degree, vdeg);
-            atomic_add_i64(&t->size, 1);
-        }
-        targetComm[i] = maxIndex;
-    }
-}
-
-// wave-per-vertex hub path, slot mode (see k4_sweep_hi's header note;
-// at p==1 a global tail id IS the local vertex id). The wave-reduce
-// tie-break order rides a packed (label << 32 | slot) value, so label
-// order decides and the slot comes along for free.
-__global__ __launch_bounds__(256) void k4_sweep_hi_p1(
-    i64 nhi, i64 lnv, const unsigned *__restrict__ perm,
-    const unsigned *__restrict__ deg_int, const unsigned *__restrict__ sigma,
-    const i64 *__restrict__ xadj,
-    const int *__restrict__ tidx32, const unsigned *__restrict__ currComm,
-    const double *__restrict__ vDegree, const Cinfo *__restrict__ cinfo,
-    Cinfo *__restrict__ cupd, double constant,
-    unsigned *__restrict__ targetComm, double *__restrict__ clusterWeight,
-    const i64 *__restrict__ hash_off, i64 *__restrict__ hkeys,
-    double *__restrict__ hacc) {
-    const int lane = threadIdx.x & 63;
-    const int wid = threadIdx.x >> 6;
-    const int wpb = blockDim.x >> 6;
-    for (i64 s = (i64)blockIdx.x * wpb + wid; s < nhi;
-         s += (i64)gridDim.x * wpb) {
-        const i64 i = perm[s];
-        const i64 v = sigma[i];
-        const int deg = (int)deg_int[i];
-        const i64 e0 = xadj[v];
-        const unsigned cc = currComm[i]; // slot
-        const unsigned ccLabel = sigma[cc];
-        const i64 hoff = hash_off[s];
-        const i64 cap = hash_off[s + 1] - hoff; // power of two
-        const Cinfo cci = cinfo[cc];
-        const double ccDeg = cci.degree;
-        const i64 ccSize = cci.size;
-        double c0 = 0.0, selfLoop = 0.0;
-        for (int k = lane; k < deg; k += 64) {
-            const i64 ti = tidx32[e0 + k]; // pre-translated internal index
-            const double w = 1.0;          // hub path is unit-only
-            if (ti == i) selfLoop += w;
-            const i64 tcomm = (i64)currComm[ti];
-            if (tcomm == (i64)cc) { c0 += w; continue; }
-            i64 pos = (i64)(((uint64_t)tcomm * 0x9E3779B97F4A7C15ull) >> 32) &
-                      (cap - 1);
-            for (;;) {
-                const i64 prev = (i64)atomicCAS(
-                    (unsigned long long *)&hkeys[hoff + pos],
-                    (unsigned long long)(-1ll), (unsigned long long)tcomm);
-                if (prev == -1 || prev == tcomm) {
-                    atomicAdd(&hacc[hoff + pos], w);
-                    break;
-                }
-                pos = (pos + 1) & (cap - 1);
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            c0 += __shfl_down(c0, off, 64);
-            selfLoop += __shfl_down(selfLoop, off, 64);
-        }
-        c0 = __shfl(c0, 0, 64);
-        selfLoop = __shfl(selfLoop, 0, 64);
-        const double vdeg = vDegree[i];
-        const double eix = c0 - selfLoop;
-        const double ax = ccDeg - vdeg;
-        double bg = 0.0;
-        i64 bl = INT64_MAX, bs = 0; // bl = (label << 32) | slot
-        for (i64 t = lane; t < cap; t += 64) {
-            const i64 y = hkeys[hoff + t];
-            if (y == -1) continue;
-            const double eiy = hacc[hoff + t];
-            const Cinfo c = cinfo[y];
-            const double ay = c.degree;
-            const i64 ysz = c.size;
-            const double g =
-                2.0 * (eiy - eix) - 2.0 * vdeg * (ay - ax) * constant;
-            const i64 yh = ((i64)sigma[y] << 32) | y;
-            if (g > bg || (g == bg && g != 0.0 && yh < bl)) {
-                bg = g;
-                bl = yh;
-                bs = ysz;
-            }
-        }
-        for (int off = 32; off > 0; off >>= 1) {
-            const double og = __shfl_down(bg, off, 64);
-            const i64 ol = __shfl_down(bl, off, 64);
-            const i64 os = __shfl_down(bs, off, 64);
-            if (og > bg || (og == bg && ol < bl)) {
-                bg = og;
-                bl = ol;
-                bs = os;
-            }
-        }
-        if (lane == 0) {
-            unsigned target =
-                (bl == INT64_MAX) ? cc : (unsigned)(bl & 0xffffffffu);
-            const unsigned tLabel =
-                (bl == INT64_MAX) ? ccLabel : (unsigned)(bl >> 32);
-            if (bs == 1 && ccSize == 1 && tLabel > ccLabel)
-                target = cc; // :224-225
-            if (deg == 0) {
-                clusterWeight[i] = 0;
-                target = cc;
-            } else {
-                clusterWeight[i] = c0;
-            }
-            if (target != cc) {
-                Cinfo *u = &cupd[cc];
-                atomicAdd(&u->degree, -vdeg);
-                atomic_add_i64(&u->size, -1);
-                Cinfo *t = &cupd[target];
-                atomicAdd(&t->degree, vdeg);
-                atomic_add_i64(&t->size, 1);
-            }
-            targetComm[i] = target;
-        }
     }
 }
 
@@ -2881,58 +2495,55 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
             return s ? atoi(s) : 2;
         }();
         const int slots = (numIters <= first_iters) ? slots_first : slots_rest;
-        auto launch_sweep = [&](auto slots_tag, auto unit_tag, i64 s0,
-                                i64 s1) {
-            constexpr int S = decltype(slots_tag)::value;
-            if (p == 1) { // u32 slots: half-size gathers, 12 B/lane LDS
-                k4_sweep_p1<S, decltype(unit_tag)::value>
-                    <<<e->sweep_grid, 256, S * 256 * 12, st>>>(
-                        s0, lnv, e->d_perm, e->d_deg, e->d_chunk_off,
-                        e->d_sell_tidx, e->d_sell_w, (const unsigned *)d_curr,
-                        e->d_vdeg, e->d_sigma, e->d_cinfo, e->d_cupd,
-                        constant, (unsigned *)d_target, e->d_cw,
-                        (unsigned *)e->d_spill_k, e->d_spill_a,
-                        e->d_spill_off);
-                return;
-            }
-            k4_sweep_mr<S, decltype(unit_tag)::value>
-                <<<grid_for(s1 - s0, 256, 2048), 256, S * 256 * 12, st>>>(
+        // Mode (the kernels' MR): view mode at p>1; at p==1 slot mode,
+        // where the u32 slot arrays ARE the view and the ghost/rc
+        // pointers are load_graph's never-read dummies (d_ghosts: null).
+        // by_flag turns a run-time bool into a std::bool_constant tag.
+        auto by_flag = [](bool b, auto f) {
+            if (b) f(std::true_type{});
+            else f(std::false_type{});
+        };
+        const unsigned *vcurr = p == 1 ? (const unsigned *)d_curr : e->d_vcurr;
+        unsigned *vtarget = p == 1 ? (unsigned *)d_target : e->d_vtarget;
+        auto range_grid = [&](i64 s0, i64 s1) {
+            return p == 1 ? e->sweep_grid : grid_for(s1 - s0, 256, 2048);
+        };
+        auto launch_sweep = [&](auto mr_tag, auto slots_tag, auto unit_tag,
+                                i64 s0, i64 s1) {
+            constexpr int S = decltype(slots_tag)::value; // 12 B/lane LDS
+            k4_sweep<decltype(mr_tag)::value, S, decltype(unit_tag)::value>
+                <<<range_grid(s0, s1), 256, S * 256 * 12, st>>>(
                     s0, s1, lnv, e->base, e->d_perm, e->d_deg,
-                    e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, e->d_vcurr,
+                    e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, vcurr,
                     e->d_vghost, e->d_vdeg, e->d_sigma, e->d_cinfo,
                     e->d_cupd, e->d_rc_ids, e->d_rc_info, e->d_rcu,
-                    constant, e->d_vtarget, e->d_cw,
+                    constant, vtarget, e->d_cw,
                     (unsigned *)e->d_spill_k, e->d_spill_a, e->d_spill_off);
         };
-        auto dispatch_slots = [&](auto unit_tag, i64 s0, i64 s1) {
+        auto dispatch_slots = [&](auto mr_tag, auto unit_tag, i64 s0,
+                                  i64 s1) {
+            auto go = [&](auto slots_tag) {
+                launch_sweep(mr_tag, slots_tag, unit_tag, s0, s1);
+            };
             switch (slots) {
-            case 4: launch_sweep(std::integral_constant<int, 4>{}, unit_tag, s0, s1); break;
-            case 12: launch_sweep(std::integral_constant<int, 12>{}, unit_tag, s0, s1); break;
-            case 16: launch_sweep(std::integral_constant<int, 16>{}, unit_tag, s0, s1); break;
-            case 24: launch_sweep(std::integral_constant<int, 24>{}, unit_tag, s0, s1); break;
-            case 32: launch_sweep(std::integral_constant<int, 32>{}, unit_tag, s0, s1); break;
-            case 48: launch_sweep(std::integral_constant<int, 48>{}, unit_tag, s0, s1); break;
-            default: launch_sweep(std::integral_constant<int, 8>{}, unit_tag, s0, s1); break;
+            case 4: go(std::integral_constant<int, 4>{}); break;
+            case 12: go(std::integral_constant<int, 12>{}); break;
+            case 16: go(std::integral_constant<int, 16>{}); break;
+            case 24: go(std::integral_constant<int, 24>{}); break;
+            case 32: go(std::integral_constant<int, 32>{}); break;
+            case 48: go(std::integral_constant<int, 48>{}); break;
+            default: go(std::integral_constant<int, 8>{}); break;
             }
         };
-        auto launch_iter1 = [&](auto unit_tag, auto lblasc_tag, i64 s0,
-                                i64 s1) {
-            if (p == 1) {
-                k4_sweep_iter1_p1<decltype(unit_tag)::value,
-                                  decltype(lblasc_tag)::value>
-                    <<<e->sweep_grid, 256, 0, st>>>(
-                        s0, lnv, e->d_perm, e->d_deg, e->d_chunk_off,
-                        e->d_sell_tidx, e->d_sell_w, e->d_vdeg, e->d_sigma,
-                        e->d_cupd, constant, (unsigned *)d_target, e->d_cw);
-                return;
-            }
-            k4_sweep_iter1_mr<decltype(unit_tag)::value,
-                              decltype(lblasc_tag)::value>
-                <<<grid_for(s1 - s0, 256, 2048), 256, 0, st>>>(
+        auto launch_iter1 = [&](auto mr_tag, auto unit_tag, auto lblasc_tag,
+                                i64 s0, i64 s1) {
+            k4_sweep_iter1<decltype(mr_tag)::value, decltype(unit_tag)::value,
+                           decltype(lblasc_tag)::value>
+                <<<range_grid(s0, s1), 256, 0, st>>>(
                     s0, s1, lnv, e->base, e->d_perm, e->d_deg,
                     e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, e->d_vghost,
                     e->d_ghosts, e->d_vdeg, e->d_sigma, e->d_cupd,
-                    e->d_rc_info, e->d_rcu, constant, e->d_vtarget, e->d_cw);
+                    e->d_rc_info, e->d_rcu, constant, vtarget, e->d_cw);
         };
         if (e->nlh > 0) { // hash-aggregation bands (skewed graphs)
             HIP_CHECK(hipMemsetAsync(e->d_hkeys, 0xFF, 8 * e->hash_total,
@@ -2941,66 +2552,50 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                                    // prefix; the lane band writes on insert
                 HIP_CHECK(hipMemsetAsync(e->d_hacc, 0,
                                          8 * e->hash_hub_elems, st));
-            if (e->nlh > e->nhi) { // per-lane hash band [nhi, nlh)
-                auto launch_lh = [&](auto unit_tag) {
+            if (e->nlh > e->nhi) // per-lane hash band [nhi, nlh)
+                by_flag(e->unit_weights, [&](auto unit_tag) {
                     k4_sweep_lh<decltype(unit_tag)::value>
                         <<<grid_for(e->nlh - e->nhi), 256, 0, st>>>(
                             e->nhi, e->nlh, lnv, e->base, e->d_perm,
                             e->d_deg, e->d_chunk_off, e->d_sell_tidx,
-                            e->d_sell_w,
-                            p == 1 ? (const unsigned *)d_curr : e->d_vcurr,
-                            e->d_vghost, e->d_vdeg, e->d_sigma, e->d_cinfo,
-                            e->d_cupd, e->d_rc_ids, e->d_rc_info, e->d_rcu,
-                            constant,
-                            p == 1 ? (unsigned *)d_target : e->d_vtarget,
+                            e->d_sell_w, vcurr, e->d_vghost, e->d_vdeg,
+                            e->d_sigma, e->d_cinfo, e->d_cupd, e->d_rc_ids,
+                            e->d_rc_info, e->d_rcu, constant, vtarget,
                             e->d_cw, e->d_hash_off, e->d_hkeys, e->d_hacc,
                             e->d_lh_list);
-                };
-                if (e->unit_weights)
-                    launch_lh(std::integral_constant<bool, true>{});
-                else
-                    launch_lh(std::integral_constant<bool, false>{});
-            }
-            if (e->nhi > 0 && p == 1)
-                k4_sweep_hi_p1<<<grid_for(e->nhi * 64, 256, 2048), 256, 0,
-                                 st>>>(
-                    e->nhi, lnv, e->d_perm, e->d_deg, e->d_sigma,
-                    e->d_xadj, e->d_tidx32,
-                    (const unsigned *)d_curr, e->d_vdeg, e->d_cinfo,
-                    e->d_cupd, constant, (unsigned *)d_target, e->d_cw,
-                    e->d_hash_off, e->d_hkeys, e->d_hacc);
-            else if (e->nhi > 0)
-            k4_sweep_hi_mr<<<grid_for(e->nhi * 64, 256, 2048), 256, 0,
-                             st>>>(
-                e->nhi, lnv, e->base, e->d_perm, e->d_deg,
-                e->d_sigma, e->d_xadj, e->d_tidx32,
-                e->d_vcurr, e->d_vghost, e->d_vdeg,
-                e->d_cinfo, e->d_cupd, e->d_rc_ids, e->d_rc_info,
-                e->d_rcu, constant, e->d_vtarget, e->d_cw, e->d_hash_off,
-                e->d_hkeys, e->d_hacc);
+                });
+            if (e->nhi > 0) // wave-per-vertex hubs [0, nhi)
+                by_flag(p > 1, [&](auto mr_tag) {
+                    k4_sweep_hi<decltype(mr_tag)::value>
+                        <<<grid_for(e->nhi * 64, 256, 2048), 256, 0, st>>>(
+                            e->nhi, lnv, e->base, e->d_perm, e->d_deg,
+                            e->d_sigma, e->d_xadj, e->d_tidx32, vcurr,
+                            e->d_vghost, e->d_vdeg, e->d_cinfo, e->d_cupd,
+                            e->d_rc_ids, e->d_rc_info, e->d_rcu, constant,
+                            vtarget, e->d_cw, e->d_hash_off, e->d_hkeys,
+                            e->d_hacc);
+                });
         }
         static const bool no_iter1 = getenv("MV_NO_ITER1") != nullptr;
         auto sweep_range = [&](i64 s0, i64 s1) {
             if (s1 <= s0) return;
-            if (numIters == 1 && (e->rows_sorted || e->sell_sorted) &&
-                !no_iter1) {
-                if (e->sell_sorted) // internal order: explicit label ties
-                    launch_iter1(std::integral_constant<bool, true>{},
-                                 std::integral_constant<bool, false>{}, s0,
-                                 s1);
-                else if (e->unit_weights)
-                    launch_iter1(std::integral_constant<bool, true>{},
-                                 std::integral_constant<bool, true>{}, s0,
-                                 s1);
-                else
-                    launch_iter1(std::integral_constant<bool, false>{},
-                                 std::integral_constant<bool, true>{}, s0,
-                                 s1);
-            } else if (e->unit_weights) {
-                dispatch_slots(std::integral_constant<bool, true>{}, s0, s1);
-            } else {
-                dispatch_slots(std::integral_constant<bool, false>{}, s0, s1);
-            }
+            const std::true_type yes{};
+            const std::false_type no{};
+            by_flag(p > 1, [&](auto mr_tag) {
+                if (numIters == 1 && (e->rows_sorted || e->sell_sorted) &&
+                    !no_iter1) {
+                    if (e->sell_sorted) // internal order: explicit label ties
+                        launch_iter1(mr_tag, yes, no, s0, s1);
+                    else if (e->unit_weights)
+                        launch_iter1(mr_tag, yes, yes, s0, s1);
+                    else
+                        launch_iter1(mr_tag, no, yes, s0, s1);
+                } else {
+                    by_flag(e->unit_weights, [&](auto unit_tag) {
+                        dispatch_slots(mr_tag, unit_tag, s0, s1);
+                    });
+                }
+            });
         };
         // persist the sweep's u32 view targets as labels (p>1 only)
         auto writeback = [&](i64 s0, i64 s1) {

@@ -90,8 +90,10 @@ struct mv_graph {
     std::vector<int32_t> locality_perm;
 };
 
-// BFS internal order over the LOCAL subgraph, re-seeded from the highest-
-// degree unvisited vertex per component: a cheap locality-creating layout
+// Label-propagation internal order over the LOCAL subgraph (the name is
+// historical: there is no BFS and no degree seeding): two rounds of
+// deterministic sequential label propagation, then a stable sort of the
+// vertices by (propagated label, id). A cheap locality-creating layout
 // for graphs without the generator's spatial hint (social-graph neighbors
 // land near each other, so the sweep's per-edge community gathers hit
 // cache instead of striding a random id space). Pure layout metadata —
