@@ -1192,6 +1192,57 @@ int grid_for(i64 n, int block = 256, int cap = 2048) {
     return (int)std::min<i64>(std::max<i64>(g, 1), cap);
 }
 
+// Move-only owner of one device (hipMalloc) or pinned host (hipHostMalloc)
+// allocation. reserve() is grow-only and does NOT preserve contents; it
+// floors n at one element so the pointer is never null once reserved.
+template <class T, bool PINNED = false> struct DevBuf {
+    T *ptr = nullptr;
+    i64 cap = 0; // elements
+    DevBuf() = default;
+    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) {
+        o.ptr = nullptr;
+        o.cap = 0;
+    }
+    DevBuf &operator=(DevBuf &&o) noexcept {
+        std::swap(ptr, o.ptr); // o's destructor frees what we held
+        std::swap(cap, o.cap);
+        return *this;
+    }
+    ~DevBuf() { release(); }
+    // true when it (re)allocated
+    bool reserve(i64 n) {
+        n = std::max<i64>(n, 1);
+        if (n <= cap) return false;
+        release();
+        if (PINNED)
+            HIP_CHECK(hipHostMalloc((void **)&ptr, sizeof(T) * n));
+        else
+            HIP_CHECK(hipMalloc((void **)&ptr, sizeof(T) * n));
+        cap = n;
+        return true;
+    }
+    void release() {
+        if (!ptr) return;
+        if (PINNED)
+            HIP_CHECK(hipHostFree(ptr));
+        else
+            HIP_CHECK(hipFree(ptr));
+        ptr = nullptr;
+        cap = 0;
+    }
+    T *get() const { return ptr; }
+    operator T *() const { return ptr; }
+};
+template <class T> using PinBuf = DevBuf<T, true>;
+
+// one point-to-point message of a batched exchange (see exchange())
+struct Xfer {
+    int peer;
+    void *ptr;
+    ncclDataType_t ty;
+    i64 count; // elements of ty
+};
+
 } // namespace
 
 // ------------------------------------------------------------------------
@@ -1208,11 +1259,7 @@ struct mv_lb_session {
     int count = 0;
     uint64_t gen = 0;
     struct Post {
-        const void *send = nullptr;
-        const void *send2 = nullptr; // delta mode: chg_idx
-        const void *send3 = nullptr; // delta mode: chg_lab
-        const int64_t *soff = nullptr;
-        size_t eb = 0;
+        const std::vector<Xfer> *sends = nullptr; // exchange(): my send list
         const double *red = nullptr;
         std::vector<int64_t> cnts;
     };
@@ -1231,7 +1278,119 @@ struct mv_lb_session {
     }
 };
 
-struct mv_engine {
+// Everything load_graph / run derive from ONE graph: the device image, the
+// per-run halo state and the logical sizes that go with them. A reload
+// replaces the whole value (free_graph_state), so a member added here needs
+// no separate reset.
+struct mv_graph_state {
+    int overlap = 0;               // this run overlaps #1a (p>1, !skewed)
+    i64 nexp = 0;                  // SELL positions [0,nexp) = exported
+
+    // graph (device)
+    i64 nv = 0, lnv = 0, lne = 0, base = 0, bound = 0;
+    int sort_bits = 64; // ceil(log2(nv)): radix sort width for id keys
+    std::vector<i64> parts_h;
+    DevBuf<i64> d_parts;
+    DevBuf<i64> d_xadj;
+    DevBuf<i64> d_tails;   // raw global tails (kept for setup)
+    DevBuf<double> d_ew;   // edge weights (CSR order)
+    int unit_weights = 1;
+    int rows_sorted = 1; // per-row tails ascending (reference CSR order)
+    int sell_sorted = 0; // SELL rows re-sorted by internal index (unit)
+    i64 max_degree = 0;
+
+    // internal layout
+    DevBuf<unsigned> d_sigma;     // internal -> original local id
+    DevBuf<unsigned> d_sigma_inv; // original local id -> internal
+    int has_hint = 0;
+
+    // SELL-64 image (built in the per-run setup span)
+    DevBuf<unsigned> d_deg;          // degree per INTERNAL index
+    DevBuf<unsigned> d_iota, d_perm; // SELL pos -> internal
+    DevBuf<i64> d_chunk_off;         // nchunks+1 element offsets
+    i64 nchunks = 0;
+    DevBuf<int> d_sell_tidx;
+    DevBuf<double> d_sell_w; // weighted graphs only
+
+    // per-run state (device)
+    DevBuf<i64> d_curr, d_past, d_target;
+    DevBuf<double> d_vdeg, d_cw;
+    DevBuf<Cinfo> d_cinfo, d_cupd;
+    DevBuf<double> d_partials; // 2 * nblocks
+    PinBuf<double> h_partials; // pinned mirror (pageable D2H costs
+                               // ~40 us/iteration in staging latency)
+    DevBuf<double> d_red;      // 2 doubles for allreduce
+
+    // ghosts / halo
+    DevBuf<i64> d_ghosts; // sorted unique remote tails
+    i64 nghost = 0;
+    // u32 community views (multi-rank sweeps; rebuilt per iteration from
+    // the persistent LABEL arrays once rc_ids is known)
+    DevBuf<unsigned> d_vcurr;   // lnv
+    DevBuf<unsigned> d_vghost;  // nghost
+    DevBuf<unsigned> d_vtarget; // lnv (persisted back as labels)
+    DevBuf<i64> d_svdata; // vertices peers want from me (global ids)
+    DevBuf<unsigned> d_svdata_int;
+    i64 ssz = 0;
+    std::vector<i64> send_off, recv_off; // per-peer offsets into svdata / ghosts
+    DevBuf<i64> d_scdata;                // packed comms to export
+
+    // halo #1a delta compaction (send side tracks the last label sent per
+    // export; receive side keeps the persistent ghost label image)
+    int use_delta = 0;
+    DevBuf<i64> d_last_sent;           // ssz, init -1 (all changed)
+    DevBuf<unsigned> d_chg_idx;        // ssz, segment-based layout
+    DevBuf<i64> d_chg_lab;             // ssz
+    DevBuf<unsigned long long> d_chg_cnt; // nranks counters
+    DevBuf<i64> d_cntmat;              // nranks*nranks image, every count
+                                       // allgather (allgather_counts)
+    PinBuf<i64> h_cntmat;              // pinned mirror (delta counts)
+    DevBuf<i64> d_soff;                // send_off on device (nranks+1)
+    DevBuf<i64> d_ghost_labels;        // nghost persistent labels
+    DevBuf<unsigned> d_rchg_idx;       // nghost recv compact indices
+    DevBuf<i64> d_rchg_lab;            // nghost recv compact labels
+
+    // remote community info (per iteration)
+    DevBuf<i64> d_cand, d_cand_sorted;
+    DevBuf<i64> d_rc_ids;
+    DevBuf<Info16> d_rc_info; // aligned with rc_ids
+    DevBuf<Info16> d_rcu;     // remoteCupdate accumulators
+    DevBuf<i64> d_req_ids;    // ids other ranks requested from me
+    DevBuf<Info16> d_req_info;
+    DevBuf<i64> d_bounds;     // nranks+1
+    DevBuf<unsigned long long> d_count;
+    DevBuf<char> d_cub_tmp; // bytes
+
+    // spill for K4 (per-thread extents; uniform for flat degree
+    // distributions, degree-prefix-sized for skewed ones)
+    DevBuf<i64> d_spill_k;
+    DevBuf<double> d_spill_a;
+    DevBuf<i64> d_spill_off;
+    int skewed = 0;
+    int sweep_grid = 0;
+
+    // hash-aggregation bands over the degree-sorted positions:
+    // [0, nhi) = wave-per-vertex hubs (unit only), [nhi, nlh) = lane-hash
+    // band, [nlh, lnv) = LDS slots + linear spill
+    i64 nhi = 0;
+    i64 nlh = 0;
+    DevBuf<unsigned> d_lh_list; // compact candidate lists (hash/2)
+    DevBuf<int> d_tidx32;   // lne pre-translated tails (hub kernels)
+    DevBuf<i64> d_hash_off; // nlh+1 slot offsets (per-vertex caps are powers of two)
+    DevBuf<i64> d_hkeys;
+    DevBuf<double> d_hacc;
+    i64 hash_total = 0;     // slots in use (the per-iteration key reset)
+    i64 hash_hub_elems = 0; // prefix the wave kernel atomics into (needs
+                            // zeroed accumulators each iteration)
+
+    // trace
+    i64 *trace_target = nullptr;
+    double *trace_mod = nullptr;
+    int trace_cap = 0;
+    DevBuf<i64> d_trace_tmp;
+};
+
+struct mv_engine : mv_graph_state {
     int device = 0, rank = 0, nranks = 1;
     ncclComm_t comm = nullptr;
     ncclComm_t comm2 = nullptr; // halo #1a's communicator (overlap mode)
@@ -1242,115 +1401,6 @@ struct mv_engine {
     hipEvent_t ev_p2 = nullptr;    // full sweep + writeback done [stream]
     hipEvent_t ev_cinfo = nullptr; // K6 + delta application done [stream]
     hipEvent_t ev_halo = nullptr;  // next-iteration pipeline done [stream2]
-    i64 *d_cnt_all = nullptr;      // persistent p*p counts buffer
-    int overlap = 0;               // this run overlaps #1a (p>1, !skewed)
-    i64 nexp = 0;                  // SELL positions [0,nexp) = exported
-
-    // graph (device)
-    i64 nv = 0, lnv = 0, lne = 0, base = 0, bound = 0;
-    int sort_bits = 64; // ceil(log2(nv)): radix sort width for id keys
-    std::vector<i64> parts_h;
-    i64 *d_parts = nullptr;
-    i64 *d_xadj = nullptr;
-    i64 *d_tails = nullptr;   // raw global tails (kept for setup)
-    double *d_ew = nullptr;   // edge weights (CSR order)
-    int unit_weights = 1;
-    int rows_sorted = 1; // per-row tails ascending (reference CSR order)
-    int sell_sorted = 0; // SELL rows re-sorted by internal index (unit)
-    i64 max_degree = 0;
-
-    // internal layout
-    unsigned *d_sigma = nullptr;     // internal -> original local id
-    unsigned *d_sigma_inv = nullptr; // original local id -> internal
-    int has_hint = 0;
-
-    // SELL-64 image (built in the per-run setup span)
-    unsigned *d_deg = nullptr;       // degree per INTERNAL index
-    unsigned *d_iota = nullptr, *d_perm = nullptr; // SELL pos -> internal
-    i64 *d_chunk_off = nullptr;      // nchunks+1 element offsets
-    i64 nchunks = 0, sell_elems = 0;
-    int *d_sell_tidx = nullptr;
-    double *d_sell_w = nullptr;
-
-    // per-run state (device)
-    i64 *d_curr = nullptr, *d_past = nullptr, *d_target = nullptr;
-    double *d_vdeg = nullptr, *d_cw = nullptr;
-    Cinfo *d_cinfo = nullptr, *d_cupd = nullptr;
-    double *d_partials = nullptr; // 2 * nblocks
-    double *h_partials = nullptr; // pinned mirror (pageable D2H costs
-                                  // ~40 us/iteration in staging latency)
-    double *d_red = nullptr;      // 2 doubles for allreduce
-
-    // ghosts / halo
-    i64 *d_ghosts = nullptr;     // sorted unique remote tails
-    i64 nghost = 0;
-    // u32 community views (multi-rank sweeps; rebuilt per iteration from
-    // the persistent LABEL arrays once rc_ids is known)
-    unsigned *d_vcurr = nullptr;   // lnv
-    unsigned *d_vghost = nullptr;  // nghost
-    unsigned *d_vtarget = nullptr; // lnv (persisted back as labels)
-    i64 *d_svdata = nullptr;     // vertices peers want from me (global ids)
-    unsigned *d_svdata_int = nullptr;
-    i64 ssz = 0;
-    std::vector<i64> send_off, recv_off; // per-peer offsets into svdata / ghosts
-    i64 *d_scdata = nullptr;             // packed comms to export
-
-    // halo #1a delta compaction (send side tracks the last label sent per
-    // export; receive side keeps the persistent ghost label image)
-    int use_delta = 0;
-    i64 *d_last_sent = nullptr;            // ssz, init -1 (all changed)
-    unsigned *d_chg_idx = nullptr;         // ssz, segment-based layout
-    i64 *d_chg_lab = nullptr;              // ssz
-    unsigned long long *d_chg_cnt = nullptr; // nranks counters
-    i64 *d_cntmat = nullptr;               // nranks*nranks allgather image
-    i64 *h_cntmat = nullptr;               // pinned mirror
-    i64 *d_soff = nullptr;                 // send_off on device (nranks+1)
-    i64 *d_ghost_labels = nullptr;         // nghost persistent labels
-    unsigned *d_rchg_idx = nullptr;        // nghost recv compact indices
-    i64 *d_rchg_lab = nullptr;             // nghost recv compact labels
-
-    // remote community info (per iteration)
-    i64 rc_cap = 0;
-    i64 *d_cand = nullptr, *d_cand_sorted = nullptr;
-    i64 *d_rc_ids = nullptr;
-    Info16 *d_rc_info = nullptr; // aligned with rc_ids
-    Info16 *d_rcu = nullptr;     // remoteCupdate accumulators
-    i64 req_cap = 0;
-    i64 *d_req_ids = nullptr;    // ids other ranks requested from me
-    Info16 *d_req_info = nullptr;
-    i64 *d_bounds = nullptr;     // nranks+1
-    unsigned long long *d_count = nullptr;
-    void *d_cub_tmp = nullptr;
-    size_t cub_tmp_bytes = 0;
-
-    // spill for K4 (per-thread extents; uniform for flat degree
-    // distributions, degree-prefix-sized for skewed ones)
-    i64 *d_spill_k = nullptr;
-    double *d_spill_a = nullptr;
-    i64 *d_spill_off = nullptr;
-    i64 spill_elems = 0;
-    int skewed = 0;
-    int sweep_grid = 0;
-
-    // hash-aggregation bands over the degree-sorted positions:
-    // [0, nhi) = wave-per-vertex hubs (unit only), [nhi, nlh) = lane-hash
-    // band, [nlh, lnv) = LDS slots + linear spill
-    i64 nhi = 0;
-    i64 nlh = 0;
-    unsigned *d_lh_list = nullptr; // compact candidate lists (hash/2)
-    int *d_tidx32 = nullptr;   // lne pre-translated tails (hub kernels)
-    i64 *d_hash_off = nullptr; // nlh+1 slot offsets (per-vertex caps are powers of two)
-    i64 *d_hkeys = nullptr;
-    double *d_hacc = nullptr;
-    i64 hash_total = 0;
-    i64 hash_hub_elems = 0; // prefix the wave kernel atomics into (needs
-                            // zeroed accumulators each iteration)
-
-    // trace
-    i64 *trace_target = nullptr;
-    double *trace_mod = nullptr;
-    int trace_cap = 0;
-    i64 *d_trace_tmp = nullptr;
 
     mv_stats stats{};
     std::vector<hipEvent_t> ev_pool;
@@ -1367,7 +1417,40 @@ struct mv_engine {
 };
 
 static void build_sell(mv_engine *e);
-static void free_graph_state(mv_engine *e);
+
+// free everything a previous load_graph/run allocated (engines may be
+// re-pointed at a new graph). The caller has set the device.
+static void free_graph_state(mv_engine *e) {
+    // this also clears trace_target / trace_mod / trace_cap: a stale trace
+    // against a freed d_trace_tmp (or a new lnv) would fault, so re-arm via
+    // mv_engine_set_trace after every load
+    static_cast<mv_graph_state &>(*e) = mv_graph_state{};
+}
+
+// the part both constructors share: device check, streams and events
+static mv_engine *engine_new(const char *who, int device, int rank,
+                             int nranks) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {
+        std::fprintf(stderr,
+                     "%s: no HIP device %d (found %d). The MI355X engine "
+                     "has no CPU fallback.\n",
+                     who, device, ndev);
+        return nullptr;
+    }
+    auto *e = new mv_engine;
+    e->device = device;
+    e->rank = rank;
+    e->nranks = nranks;
+    HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipStreamCreate(&e->stream));
+    HIP_CHECK(hipStreamCreate(&e->stream2));
+    HIP_CHECK(hipEventCreate(&e->ev_p1));
+    HIP_CHECK(hipEventCreate(&e->ev_p2));
+    HIP_CHECK(hipEventCreate(&e->ev_cinfo));
+    HIP_CHECK(hipEventCreate(&e->ev_halo));
+    return e;
+}
 
 extern "C" {
 
@@ -1381,26 +1464,12 @@ int mv_comm_id(void *id_bytes) {
 
 mv_engine *mv_engine_create(int device, int rank, int nranks,
                             const void *comm_id) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {
-        std::fprintf(stderr,
-                     "mv_engine_create: no HIP device %d (found %d). The "
-                     "MI355X engine has no CPU fallback.\n",
-                     device, ndev);
+    if (nranks > 1 && !comm_id) {
+        std::fprintf(stderr, "mv_engine_create: nranks>1 needs comm id\n");
         return nullptr;
     }
-    auto *e = new mv_engine;
-    e->device = device;
-    e->rank = rank;
-    e->nranks = nranks;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreate(&e->stream));
-    if (nranks > 1) {
-        if (!comm_id) {
-            std::fprintf(stderr, "mv_engine_create: nranks>1 needs comm id\n");
-            delete e;
-            return nullptr;
-        }
+    mv_engine *e = engine_new("mv_engine_create", device, rank, nranks);
+    if (e && nranks > 1) {
         ncclUniqueId id;
         std::memcpy(&id, comm_id, sizeof(id));
         NCCL_CHECK(ncclCommInitRank(&e->comm, nranks, id, rank));
@@ -1410,11 +1479,6 @@ mv_engine *mv_engine_create(int device, int rank, int nranks,
         if (!getenv("MV_NO_OVERLAP"))
             NCCL_CHECK(ncclCommSplit(e->comm, 0, rank, &e->comm2, nullptr));
     }
-    HIP_CHECK(hipStreamCreate(&e->stream2));
-    HIP_CHECK(hipEventCreate(&e->ev_p1));
-    HIP_CHECK(hipEventCreate(&e->ev_p2));
-    HIP_CHECK(hipEventCreate(&e->ev_cinfo));
-    HIP_CHECK(hipEventCreate(&e->ev_halo));
     return e;
 }
 
@@ -1424,29 +1488,12 @@ void mv_lb_destroy(mv_lb_session *s) { delete s; }
 
 mv_engine *mv_engine_create_lb(int device, int rank, int nranks,
                                mv_lb_session *s) {
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {
-        std::fprintf(stderr,
-                     "mv_engine_create_lb: no HIP device %d (found %d)\n",
-                     device, ndev);
-        return nullptr;
-    }
     if (!s || s->nranks != nranks) {
         std::fprintf(stderr, "mv_engine_create_lb: bad session\n");
         return nullptr;
     }
-    auto *e = new mv_engine;
-    e->device = device;
-    e->rank = rank;
-    e->nranks = nranks;
-    e->lb = s;
-    HIP_CHECK(hipSetDevice(device));
-    HIP_CHECK(hipStreamCreate(&e->stream));
-    HIP_CHECK(hipStreamCreate(&e->stream2));
-    HIP_CHECK(hipEventCreate(&e->ev_p1));
-    HIP_CHECK(hipEventCreate(&e->ev_p2));
-    HIP_CHECK(hipEventCreate(&e->ev_cinfo));
-    HIP_CHECK(hipEventCreate(&e->ev_halo));
+    mv_engine *e = engine_new("mv_engine_create_lb", device, rank, nranks);
+    if (e) e->lb = s;
     return e;
 }
 
@@ -1464,69 +1511,6 @@ void mv_engine_destroy(mv_engine *e) {
     if (e->stream2) (void)hipStreamDestroy(e->stream2);
     if (e->stream) (void)hipStreamDestroy(e->stream);
     delete e;
-}
-
-// free everything a previous load_graph/run allocated (engines may be
-// re-pointed at a new graph)
-static void free_graph_state(mv_engine *e) {
-    for (void **p : {(void **)&e->d_parts, (void **)&e->d_xadj,
-                     (void **)&e->d_tails, (void **)&e->d_ew,
-                     (void **)&e->d_sigma, (void **)&e->d_sigma_inv,
-                     (void **)&e->d_deg, (void **)&e->d_iota,
-                     (void **)&e->d_perm, (void **)&e->d_chunk_off,
-                     (void **)&e->d_sell_tidx, (void **)&e->d_sell_w,
-                     (void **)&e->d_curr, (void **)&e->d_past,
-                     (void **)&e->d_target, (void **)&e->d_vdeg,
-                     (void **)&e->d_cw, (void **)&e->d_cinfo,
-                     (void **)&e->d_cupd, (void **)&e->d_partials,
-                     (void **)&e->d_red, (void **)&e->d_count,
-                     (void **)&e->d_bounds, (void **)&e->d_ghosts,
-                     (void **)&e->d_vcurr, (void **)&e->d_vghost,
-                     (void **)&e->d_vtarget, (void **)&e->d_svdata,
-                     (void **)&e->d_svdata_int, (void **)&e->d_scdata,
-                     (void **)&e->d_cand, (void **)&e->d_cand_sorted,
-                     (void **)&e->d_rc_ids, (void **)&e->d_rc_info,
-                     (void **)&e->d_rcu, (void **)&e->d_req_ids,
-                     (void **)&e->d_req_info, (void **)&e->d_cub_tmp,
-                     (void **)&e->d_spill_k, (void **)&e->d_spill_a,
-                     (void **)&e->d_spill_off, (void **)&e->d_hash_off,
-                     (void **)&e->d_hkeys, (void **)&e->d_hacc,
-                     (void **)&e->d_tidx32, (void **)&e->d_lh_list,
-                     (void **)&e->d_last_sent, (void **)&e->d_chg_idx,
-                     (void **)&e->d_chg_lab, (void **)&e->d_chg_cnt,
-                     (void **)&e->d_cntmat, (void **)&e->d_soff,
-                     (void **)&e->d_ghost_labels, (void **)&e->d_rchg_idx,
-                     (void **)&e->d_rchg_lab, (void **)&e->d_cnt_all,
-                     (void **)&e->d_trace_tmp}) {
-        if (*p) {
-            HIP_CHECK(hipFree(*p));
-            *p = nullptr;
-        }
-    }
-    if (e->h_partials) {
-        HIP_CHECK(hipHostFree(e->h_partials));
-        e->h_partials = nullptr;
-    }
-    if (e->h_cntmat) {
-        HIP_CHECK(hipHostFree(e->h_cntmat));
-        e->h_cntmat = nullptr;
-    }
-    // a stale trace against a freed d_trace_tmp (or a new lnv) would fault:
-    // re-arm via mv_engine_set_trace after every load
-    e->trace_target = nullptr;
-    e->trace_mod = nullptr;
-    e->trace_cap = 0;
-    e->sell_elems = 0;
-    e->spill_elems = 0;
-    e->rc_cap = 0;
-    e->req_cap = 0;
-    e->hash_total = 0;
-    e->nghost = 0;
-    e->ssz = 0;
-    e->nhi = 0;
-    e->nlh = 0;
-    e->hash_hub_elems = 0;
-    e->cub_tmp_bytes = 0;
 }
 
 int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
@@ -1561,27 +1545,27 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
         for (i64 k = xadj[i] + 1; k < xadj[i + 1]; k++)
             if (tails_h[k - 1] > tails_h[k]) { e->rows_sorted = 0; break; }
 
-    HIP_CHECK(hipMalloc(&e->d_parts, 8 * (e->nranks + 1)));
+    e->d_parts.reserve(e->nranks + 1);
     HIP_CHECK(hipMemcpy(e->d_parts, e->parts_h.data(), 8 * (e->nranks + 1),
                         hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc(&e->d_xadj, 8 * (lnv + 1)));
+    e->d_xadj.reserve(lnv + 1);
     HIP_CHECK(hipMemcpy(e->d_xadj, xadj, 8 * (lnv + 1), hipMemcpyHostToDevice));
-    HIP_CHECK(hipMalloc(&e->d_tails, 8 * std::max<i64>(lne, 1)));
+    e->d_tails.reserve(lne);
     HIP_CHECK(hipMemcpy(e->d_tails, mv_graph_tails(g), 8 * lne,
                         hipMemcpyHostToDevice));
     // unit graphs never read edge weights on device (K1 counts rows, the
     // SELL carries no weight stream): skip the 8*lne upload entirely
     if (e->unit_weights) {
-        HIP_CHECK(hipMalloc(&e->d_ew, 16)); // never-null dummy
+        e->d_ew.reserve(2); // never-null dummy
     } else {
-        HIP_CHECK(hipMalloc(&e->d_ew, 8 * std::max<i64>(lne, 1)));
+        e->d_ew.reserve(lne);
         HIP_CHECK(hipMemcpy(e->d_ew, w, 8 * lne, hipMemcpyHostToDevice));
     }
 
     // internal layout: the builder's spatial hint, or identity (the
     // degree-sort fallback then runs in the per-run setup)
-    HIP_CHECK(hipMalloc(&e->d_sigma, 4 * std::max<i64>(lnv, 1)));
-    HIP_CHECK(hipMalloc(&e->d_sigma_inv, 4 * std::max<i64>(lnv, 1)));
+    e->d_sigma.reserve(lnv);
+    e->d_sigma_inv.reserve(lnv);
     const int32_t *hint = mv_graph_locality_hint(g);
     e->has_hint = hint != nullptr;
     if (hint) {
@@ -1592,30 +1576,30 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     k_invert_perm<<<grid_for(lnv), 256>>>(lnv, e->d_sigma, e->d_sigma_inv);
 
     e->nchunks = (lnv + 63) / 64;
-    HIP_CHECK(hipMalloc(&e->d_deg, 4 * std::max<i64>(lnv, 1)));
-    HIP_CHECK(hipMalloc(&e->d_iota, 4 * std::max<i64>(lnv, 1)));
-    HIP_CHECK(hipMalloc(&e->d_perm, 4 * std::max<i64>(lnv, 1)));
-    HIP_CHECK(hipMalloc(&e->d_chunk_off, 8 * (e->nchunks + 1)));
+    e->d_deg.reserve(lnv);
+    e->d_iota.reserve(lnv);
+    e->d_perm.reserve(lnv);
+    e->d_chunk_off.reserve(e->nchunks + 1);
 
-    HIP_CHECK(hipMalloc(&e->d_curr, 8 * lnv));
-    HIP_CHECK(hipMalloc(&e->d_past, 8 * lnv));
-    HIP_CHECK(hipMalloc(&e->d_target, 8 * lnv));
-    HIP_CHECK(hipMalloc(&e->d_vdeg, 8 * lnv));
-    HIP_CHECK(hipMalloc(&e->d_cw, 8 * lnv));
-    HIP_CHECK(hipMalloc(&e->d_cinfo, sizeof(Cinfo) * lnv));
-    HIP_CHECK(hipMalloc(&e->d_cupd, sizeof(Cinfo) * lnv));
+    e->d_curr.reserve(lnv);
+    e->d_past.reserve(lnv);
+    e->d_target.reserve(lnv);
+    e->d_vdeg.reserve(lnv);
+    e->d_cw.reserve(lnv);
+    e->d_cinfo.reserve(lnv);
+    e->d_cupd.reserve(lnv);
     // never-null dummies for pointers that stay unused at nranks==1 but
     // may still be address-computed by if-converted loads
-    if (!e->d_vghost) HIP_CHECK(hipMalloc(&e->d_vghost, 16));
-    if (!e->d_rc_ids) HIP_CHECK(hipMalloc(&e->d_rc_ids, 16));
-    if (!e->d_rc_info) HIP_CHECK(hipMalloc(&e->d_rc_info, sizeof(Info16)));
-    if (!e->d_rcu) HIP_CHECK(hipMalloc(&e->d_rcu, sizeof(Info16)));
-    HIP_CHECK(hipMalloc(&e->d_count, 8));
-    HIP_CHECK(hipMalloc(&e->d_bounds, 8 * (e->nranks + 1)));
-    HIP_CHECK(hipMalloc(&e->d_red, 16));
+    e->d_vghost.reserve(4);
+    e->d_rc_ids.reserve(2);
+    e->d_rc_info.reserve(1);
+    e->d_rcu.reserve(1);
+    e->d_count.reserve(1);
+    e->d_bounds.reserve(e->nranks + 1);
+    e->d_red.reserve(2);
     const int nblocks = grid_for(lnv);
-    HIP_CHECK(hipMalloc(&e->d_partials, 16 * nblocks));
-    HIP_CHECK(hipHostMalloc(&e->h_partials, 16 * nblocks));
+    e->d_partials.reserve(2 * nblocks);
+    e->h_partials.reserve(2 * nblocks);
 
     // K4 geometry: 256-thread blocks, 8 LDS slots/lane (32 KiB/block ->
     // 4-5 blocks/CU). Spill sizing: uniform per-thread max_degree extents
@@ -1626,7 +1610,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     e->sweep_grid = grid_for(lnv, 256, 2048);
     e->skewed = e->max_degree > 256;
     const i64 nthreads = (i64)e->sweep_grid * 256;
-    HIP_CHECK(hipMalloc(&e->d_spill_off, 8 * nthreads));
+    e->d_spill_off.reserve(nthreads);
 
     if (e->nranks == 1) build_sell(e);
     HIP_CHECK(hipDeviceSynchronize());
@@ -1640,91 +1624,146 @@ void mv_engine_set_trace(mv_engine *e, int64_t *target_trace, double *mod_trace,
     e->trace_target = target_trace;
     e->trace_mod = mod_trace;
     e->trace_cap = cap;
-    if (target_trace && !e->d_trace_tmp)
-        HIP_CHECK(hipMalloc(&e->d_trace_tmp, 8 * std::max<i64>(e->lnv, 1)));
+    if (target_trace) e->d_trace_tmp.reserve(e->lnv);
 }
 
 void mv_engine_get_stats(const mv_engine *e, mv_stats *out) { *out = e->stats; }
 
-// helper: alltoallv; offsets in elements. RCCL grouped send/recv on the
-// product path, device-to-device copies on the loopback harness.
-static void rccl_alltoallv(mv_engine *e, const void *send, const i64 *soff,
-                           void *recv, const i64 *roff, size_t elem_bytes,
-                           ncclDataType_t ty, size_t ty_bytes,
-                           ncclComm_t comm, hipStream_t stream) {
+// ------------------------------------------------------------------------
+// Transport seam. Three primitives — exchange(), allgather_counts() and
+// comm_allreduce_host() — each with an RCCL arm (the product path) and a
+// loopback arm (device-to-device copies + host barriers). The protocol code
+// that calls them builds ONE plan per exchange and never asks which arm runs.
+
+static bool has_second_channel(const mv_engine *e) {
+    return e->comm2 || e->lb; // loopback needs no second communicator
+}
+
+static size_t ty_bytes(ncclDataType_t ty) {
+    if (ty == ncclChar) return 1;
+    if (ty == ncclInt64) return 8;
+    std::fprintf(stderr, "exchange: unsupported datatype %d\n", (int)ty);
+    std::abort();
+}
+
+// Batched point-to-point exchange. Both lists ascend by peer and may hold
+// several entries per peer; the k-th send of rank a to rank b lands in
+// b's k-th recv from a. RCCL: one group, peer by peer, a peer's sends then
+// its recvs. Loopback: each rank pulls the sends addressed to it.
+static void exchange(mv_engine *e, const std::vector<Xfer> &sends,
+                     const std::vector<Xfer> &recvs, ncclComm_t comm,
+                     hipStream_t stream) {
+    const int p = e->nranks, me = e->rank;
     if (e->lb) {
         mv_lb_session *s = e->lb;
-        // own kernels feeding `send` must be complete before peers copy
+        // own kernels feeding the sends must be complete before peers copy
         HIP_CHECK(hipStreamSynchronize(stream));
-        s->posts[e->rank].send = send;
-        s->posts[e->rank].soff = soff;
-        s->posts[e->rank].eb = elem_bytes;
+        s->posts[me].sends = &sends;
         s->barrier();
-        for (int r = 0; r < e->nranks; r++) {
-            if (r == e->rank) continue;
-            const auto &ps = s->posts[r];
-            const i64 cnt = ps.soff[e->rank + 1] - ps.soff[e->rank];
-            if (cnt != roff[r + 1] - roff[r]) {
+        size_t j = 0;
+        for (int r = 0; r < p; r++) {
+            if (r == me) continue;
+            for (const Xfer &x : *s->posts[r].sends) {
+                if (x.peer != me) continue;
+                const bool have = j < recvs.size() && recvs[j].peer == r;
+                const size_t sb = x.count * ty_bytes(x.ty);
+                const size_t rb =
+                    have ? recvs[j].count * ty_bytes(recvs[j].ty) : 0;
+                if (!have || sb != rb) {
+                    std::fprintf(stderr,
+                                 "loopback exchange mismatch: me=%d r=%d "
+                                 "sender says %zu bytes, I expect %zu\n",
+                                 me, r, sb, rb);
+                    std::abort();
+                }
+                HIP_CHECK(hipMemcpyAsync(recvs[j++].ptr, x.ptr, sb,
+                                         hipMemcpyDeviceToDevice, stream));
+            }
+            if (j < recvs.size() && recvs[j].peer == r) {
                 std::fprintf(stderr,
-                             "loopback alltoallv count mismatch: me=%d r=%d "
-                             "sender says %lld, I expect %lld (eb=%zu)\n",
-                             e->rank, r, (long long)cnt,
-                             (long long)(roff[r + 1] - roff[r]), elem_bytes);
+                             "loopback exchange mismatch: me=%d r=%d sent "
+                             "fewer messages than I expect\n",
+                             me, r);
                 std::abort();
             }
-            if (cnt > 0)
-                HIP_CHECK(hipMemcpyAsync(
-                    (char *)recv + roff[r] * elem_bytes,
-                    (const char *)ps.send + ps.soff[e->rank] * elem_bytes,
-                    cnt * elem_bytes, hipMemcpyDeviceToDevice, stream));
         }
         HIP_CHECK(hipStreamSynchronize(stream));
         s->barrier(); // senders may reuse their buffers after this
         return;
     }
     NCCL_CHECK(ncclGroupStart());
+    size_t i = 0, j = 0;
+    for (int r = 0; r < p; r++) {
+        for (; i < sends.size() && sends[i].peer == r; i++)
+            NCCL_CHECK(ncclSend(sends[i].ptr, sends[i].count, sends[i].ty, r,
+                                comm, stream));
+        for (; j < recvs.size() && recvs[j].peer == r; j++)
+            NCCL_CHECK(ncclRecv(recvs[j].ptr, recvs[j].count, recvs[j].ty, r,
+                                comm, stream));
+    }
+    NCCL_CHECK(ncclGroupEnd());
+}
+
+// alltoallv over exchange(); offsets in elements of elem_bytes, sent as
+// `ty`. Empty segments are skipped.
+static void alltoallv(mv_engine *e, const void *send, const i64 *soff,
+                      void *recv, const i64 *roff, size_t elem_bytes,
+                      ncclDataType_t ty, ncclComm_t comm, hipStream_t stream) {
+    const i64 per = (i64)(elem_bytes / ty_bytes(ty));
+    std::vector<Xfer> sends, recvs;
     for (int r = 0; r < e->nranks; r++) {
         if (r == e->rank) continue;
         const i64 scnt = soff[r + 1] - soff[r];
         const i64 rcnt = roff[r + 1] - roff[r];
         if (scnt > 0)
-            NCCL_CHECK(ncclSend((const char *)send + soff[r] * elem_bytes,
-                                scnt * elem_bytes / ty_bytes, ty, r, comm,
-                                stream));
+            sends.push_back({r, (char *)send + soff[r] * elem_bytes, ty,
+                             scnt * per});
         if (rcnt > 0)
-            NCCL_CHECK(ncclRecv((char *)recv + roff[r] * elem_bytes,
-                                rcnt * elem_bytes / ty_bytes, ty, r, comm,
-                                stream));
+            recvs.push_back({r, (char *)recv + roff[r] * elem_bytes, ty,
+                             rcnt * per});
     }
-    NCCL_CHECK(ncclGroupEnd());
+    exchange(e, sends, recvs, comm, stream);
 }
 
-// exchange per-peer counts: allgather of my nranks counts
-static void exchange_counts(mv_engine *e, const std::vector<i64> &mine,
-                            std::vector<i64> &matrix /*nranks*nranks*/,
-                            ncclComm_t comm, hipStream_t stream) {
-    matrix.resize((size_t)e->nranks * e->nranks);
+// Count allgather: my nranks counts (`mine`, on the host or on the device)
+// -> every rank's row in the host matrix (nranks*nranks). Returns with the
+// matrix complete.
+static void allgather_counts(mv_engine *e, const i64 *mine, bool on_device,
+                             i64 *matrix, ncclComm_t comm,
+                             hipStream_t stream) {
+    const int p = e->nranks;
     if (e->lb) {
         mv_lb_session *s = e->lb;
-        s->posts[e->rank].cnts = mine;
+        std::vector<int64_t> &post = s->posts[e->rank].cnts;
+        post.resize(p);
+        if (on_device) {
+            HIP_CHECK(hipMemcpyAsync(post.data(), mine, 8 * p,
+                                     hipMemcpyDeviceToHost, stream));
+            HIP_CHECK(hipStreamSynchronize(stream));
+        } else {
+            std::copy(mine, mine + p, post.begin());
+        }
         s->barrier();
-        for (int r = 0; r < e->nranks; r++)
+        for (int r = 0; r < p; r++)
             std::copy(s->posts[r].cnts.begin(), s->posts[r].cnts.end(),
-                      matrix.begin() + (size_t)r * e->nranks);
+                      matrix + (size_t)r * p);
         s->barrier();
         return;
     }
-    // persistent buffer: a hipMalloc/hipFree here would device-sync and
-    // re-serialize the overlapped pipeline
-    if (!e->d_cnt_all)
-        HIP_CHECK(hipMalloc(&e->d_cnt_all, 8 * e->nranks * e->nranks));
-    i64 *d_all = e->d_cnt_all;
-    HIP_CHECK(hipMemcpyAsync(d_all + (i64)e->rank * e->nranks, mine.data(),
-                             8 * e->nranks, hipMemcpyHostToDevice, stream));
-    NCCL_CHECK(ncclAllGather(d_all + (i64)e->rank * e->nranks, d_all,
-                             e->nranks, ncclInt64, comm, stream));
-    HIP_CHECK(hipMemcpyAsync(matrix.data(), d_all, 8 * e->nranks * e->nranks,
-                             hipMemcpyDeviceToHost, stream));
+    // persistent buffer (allocated by the first, setup-time call): a
+    // hipMalloc/hipFree here would device-sync and re-serialize the
+    // overlapped pipeline. One matrix serves every caller: each call
+    // returns only after its D2H copy has synced, and a rank issues its
+    // allgathers from one host thread.
+    e->d_cntmat.reserve((i64)p * p);
+    i64 *d_all = e->d_cntmat, *row = d_all + (i64)e->rank * p;
+    HIP_CHECK(hipMemcpyAsync(row, mine, 8 * p,
+                             on_device ? hipMemcpyDeviceToDevice
+                                       : hipMemcpyHostToDevice,
+                             stream));
+    NCCL_CHECK(ncclAllGather(row, d_all, p, ncclInt64, comm, stream));
+    HIP_CHECK(hipMemcpyAsync(matrix, d_all, 8 * p * p, hipMemcpyDeviceToHost,
+                             stream));
     HIP_CHECK(hipStreamSynchronize(stream));
 }
 
@@ -1770,17 +1809,17 @@ static void build_sell(mv_engine *e) {
         k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm);
     } else {
         k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_iota);
-        unsigned *d_degs = nullptr;
-        HIP_CHECK(hipMalloc(&d_degs, 4 * std::max<i64>(lnv, 1)));
+        DevBuf<unsigned> d_degs; // temporaries: freed with this block
+        DevBuf<char> d_tmp;
+        d_degs.reserve(lnv);
         size_t tb = 0;
         (void)hipcub::DeviceRadixSort::SortPairsDescending(
-            nullptr, tb, e->d_deg, d_degs, e->d_iota, e->d_perm, lnv, 0,
-            32, st);
-        void *d_tmp = nullptr;
-        HIP_CHECK(hipMalloc(&d_tmp, std::max<size_t>(tb, 1)));
+            nullptr, tb, e->d_deg.get(), d_degs.get(), e->d_iota.get(),
+            e->d_perm.get(), lnv, 0, 32, st);
+        d_tmp.reserve(tb);
         (void)hipcub::DeviceRadixSort::SortPairsDescending(
-            d_tmp, tb, e->d_deg, d_degs, e->d_iota, e->d_perm, lnv, 0, 32,
-            st);
+            d_tmp.get(), tb, e->d_deg.get(), d_degs.get(), e->d_iota.get(),
+            e->d_perm.get(), lnv, 0, 32, st);
         // high-degree split + per-vertex hash regions (unit: wave-per-
         // vertex atomic hash; -w: per-lane serial hash in edge order)
         std::vector<unsigned> sdeg(lnv);
@@ -1812,9 +1851,7 @@ static void build_sell(mv_engine *e) {
         e->nhi = (e->skewed && e->unit_weights) ? nhi : 0;
         e->nlh = e->skewed ? std::max<i64>(nlh, e->nhi) : 0;
         if (e->nlh > 0) {
-            if (!e->d_tidx32)
-                HIP_CHECK(hipMalloc(&e->d_tidx32,
-                                    4 * std::max<i64>(e->lne, 1)));
+            e->d_tidx32.reserve(e->lne);
             k_translate_tails<<<grid_for(e->lne), 256, 0, st>>>(
                 e->lne, e->d_tails, e->base, e->bound, e->d_sigma_inv,
                 e->d_ghosts, e->nghost, lnv, e->d_tidx32);
@@ -1828,24 +1865,17 @@ static void build_sell(mv_engine *e) {
             }
             hoff[e->nlh] = acc;
             e->hash_hub_elems = e->nhi > 0 ? hoff[e->nhi] : 0;
-            if (e->d_hash_off) HIP_CHECK(hipFree(e->d_hash_off));
-            HIP_CHECK(hipMalloc(&e->d_hash_off, 8 * (e->nlh + 1)));
+            e->d_hash_off.reserve(e->nlh + 1);
             HIP_CHECK(hipMemcpyAsync(e->d_hash_off, hoff.data(),
                                      8 * (e->nlh + 1),
                                      hipMemcpyHostToDevice, st));
-            if (acc > e->hash_total) {
-                if (e->d_hkeys) HIP_CHECK(hipFree(e->d_hkeys));
-                if (e->d_hacc) HIP_CHECK(hipFree(e->d_hacc));
-                if (e->d_lh_list) HIP_CHECK(hipFree(e->d_lh_list));
-                e->hash_total = acc;
-                HIP_CHECK(hipMalloc(&e->d_hkeys, 8 * acc));
-                HIP_CHECK(hipMalloc(&e->d_hacc, 8 * acc));
-                HIP_CHECK(hipMalloc(&e->d_lh_list, 4 * (acc / 2 + 1)));
+            e->hash_total = acc;
+            if (e->d_hkeys.reserve(acc)) { // the three grow together
+                e->d_hacc.reserve(acc);
+                e->d_lh_list.reserve(acc / 2 + 1);
             }
             HIP_CHECK(hipStreamSynchronize(st));
         }
-        HIP_CHECK(hipFree(d_tmp));
-        HIP_CHECK(hipFree(d_degs));
     }
 
     // Exports-first SELL order (halo overlap): positions [0, nexp) hold
@@ -1857,81 +1887,72 @@ static void build_sell(mv_engine *e) {
     // inside each group is preserved. Pure layout, results identical.
     e->nexp = 0;
     e->overlap = 0;
-    if (e->nranks > 1 && !e->skewed && e->ssz > 0 && (e->comm2 || e->lb) &&
+    if (e->nranks > 1 && !e->skewed && e->ssz > 0 && has_second_channel(e) &&
         !getenv("MV_NO_OVERLAP")) {
         // device-side stable partition (two hipCUB Flagged selects): the
         // host round trip cost ~ms per run at 8-GPU sizes
-        unsigned char *d_mark = nullptr, *d_flags = nullptr;
-        unsigned *d_out = nullptr;
-        i64 *d_num = nullptr;
-        HIP_CHECK(hipMalloc(&d_mark, lnv));
-        HIP_CHECK(hipMalloc(&d_flags, lnv));
-        HIP_CHECK(hipMalloc(&d_out, 4 * lnv));
-        HIP_CHECK(hipMalloc(&d_num, 8));
+        DevBuf<unsigned char> d_mark, d_flags; // freed with this block
+        DevBuf<unsigned> d_out;
+        DevBuf<i64> d_num;
+        DevBuf<char> d_tsel;
+        d_mark.reserve(lnv);
+        d_flags.reserve(lnv);
+        d_out.reserve(lnv);
+        d_num.reserve(1);
         HIP_CHECK(hipMemsetAsync(d_mark, 0, lnv, st));
         k_scatter_mark<<<grid_for(e->ssz), 256, 0, st>>>(
             e->ssz, e->d_svdata_int, d_mark);
         k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
                                                       d_flags, 0);
         size_t tsel = 0;
-        (void)hipcub::DeviceSelect::Flagged(nullptr, tsel, e->d_perm,
-                                            d_flags, d_out, d_num, lnv, st);
-        void *d_tsel = nullptr;
-        HIP_CHECK(hipMalloc(&d_tsel, std::max<size_t>(tsel, 1)));
-        (void)hipcub::DeviceSelect::Flagged(d_tsel, tsel, e->d_perm, d_flags,
-                                            d_out, d_num, lnv, st);
+        (void)hipcub::DeviceSelect::Flagged(nullptr, tsel, e->d_perm.get(),
+                                            d_flags.get(), d_out.get(),
+                                            d_num.get(), lnv, st);
+        d_tsel.reserve(tsel);
+        (void)hipcub::DeviceSelect::Flagged(d_tsel.get(), tsel,
+                                            e->d_perm.get(), d_flags.get(),
+                                            d_out.get(), d_num.get(), lnv, st);
         HIP_CHECK(hipMemcpyAsync(&e->nexp, d_num, 8, hipMemcpyDeviceToHost,
                                  st));
         HIP_CHECK(hipStreamSynchronize(st));
         k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
                                                       d_flags, 1);
-        (void)hipcub::DeviceSelect::Flagged(d_tsel, tsel, e->d_perm, d_flags,
-                                            d_out + e->nexp, d_num, lnv, st);
+        (void)hipcub::DeviceSelect::Flagged(d_tsel.get(), tsel,
+                                            e->d_perm.get(), d_flags.get(),
+                                            d_out + e->nexp, d_num.get(), lnv,
+                                            st);
         HIP_CHECK(hipMemcpyAsync(e->d_perm, d_out, 4 * lnv,
                                  hipMemcpyDeviceToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        HIP_CHECK(hipFree(d_mark));
-        HIP_CHECK(hipFree(d_flags));
-        HIP_CHECK(hipFree(d_out));
-        HIP_CHECK(hipFree(d_num));
-        HIP_CHECK(hipFree(d_tsel));
         e->overlap = 1;
     }
 
     {
-        i64 *d_sizes = nullptr;
-        HIP_CHECK(hipMalloc(&d_sizes, 8 * std::max<i64>(e->nchunks, 1)));
+        DevBuf<i64> d_sizes; // freed with this block
+        DevBuf<char> d_tmp2;
+        d_sizes.reserve(e->nchunks);
         k_chunk_sizes<<<grid_for(e->nchunks), 256, 0, st>>>(
             e->nchunks, lnv, e->d_perm, e->d_deg, d_sizes);
         HIP_CHECK(hipMemsetAsync(e->d_chunk_off, 0, 8, st));
         size_t tb2 = 0;
-        (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb2, d_sizes,
+        (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb2, d_sizes.get(),
                                          e->d_chunk_off + 1, e->nchunks,
                                          st);
-        void *d_tmp2 = nullptr;
-        HIP_CHECK(hipMalloc(&d_tmp2, std::max<size_t>(tb2, 1)));
-        (void)hipcub::DeviceScan::InclusiveSum(d_tmp2, tb2, d_sizes,
-                                         e->d_chunk_off + 1, e->nchunks,
-                                         st);
+        d_tmp2.reserve(tb2);
+        (void)hipcub::DeviceScan::InclusiveSum(d_tmp2.get(), tb2,
+                                         d_sizes.get(), e->d_chunk_off + 1,
+                                         e->nchunks, st);
         i64 total = 0;
         HIP_CHECK(hipMemcpyAsync(&total, e->d_chunk_off + e->nchunks, 8,
                                  hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
-        if (total > e->sell_elems) {
-            if (e->d_sell_tidx) HIP_CHECK(hipFree(e->d_sell_tidx));
-            if (e->d_sell_w) HIP_CHECK(hipFree(e->d_sell_w));
-            e->sell_elems = total;
-            HIP_CHECK(hipMalloc(&e->d_sell_tidx,
-                                4 * std::max<i64>(total, 1)));
-            if (!e->unit_weights)
-                HIP_CHECK(hipMalloc(&e->d_sell_w,
-                                    8 * std::max<i64>(total, 1)));
-        }
+        e->d_sell_tidx.reserve(total);
+        if (!e->unit_weights) e->d_sell_w.reserve(total);
         k_fill_sell<<<grid_for(lnv), 256, 0, st>>>(
             lnv, e->d_perm, e->d_sigma, e->d_sigma_inv, e->d_xadj,
             e->d_tails, e->d_ew, e->base, e->bound, e->d_ghosts, e->nghost,
             e->d_chunk_off, e->d_sell_tidx,
-            e->unit_weights ? nullptr : e->d_sell_w);
+            e->unit_weights ? nullptr : e->d_sell_w.get());
         // unit graphs: re-sort rows by internal index for gather locality
         // (see k_sell_sort_rows; results identical, measured +4-5%)
         e->sell_sorted = 0;
@@ -1940,8 +1961,6 @@ static void build_sell(mv_engine *e) {
                 lnv, e->d_perm, e->d_deg, e->d_chunk_off, e->d_sell_tidx);
             e->sell_sorted = 1;
         }
-        HIP_CHECK(hipFree(d_tmp2));
-        HIP_CHECK(hipFree(d_sizes));
     }
 
     // per-thread spill extents
@@ -1954,8 +1973,8 @@ static void build_sell(mv_engine *e) {
                 nthreads, per, e->d_spill_off);
             total = nthreads * per;
         } else {
-            i64 *d_need = nullptr;
-            HIP_CHECK(hipMalloc(&d_need, 8 * nthreads));
+            DevBuf<i64> d_need; // freed with this block
+            d_need.reserve(nthreads);
             k_spill_need<<<grid_for(nthreads), 256, 0, st>>>(
                 nthreads, e->nlh, lnv, e->d_perm, e->d_deg, 4, d_need);
             std::vector<i64> need(nthreads), off(nthreads);
@@ -1972,15 +1991,9 @@ static void build_sell(mv_engine *e) {
                                      8 * nthreads, hipMemcpyHostToDevice,
                                      st));
             HIP_CHECK(hipStreamSynchronize(st));
-            HIP_CHECK(hipFree(d_need));
         }
-        if (total > e->spill_elems) {
-            if (e->d_spill_k) HIP_CHECK(hipFree(e->d_spill_k));
-            if (e->d_spill_a) HIP_CHECK(hipFree(e->d_spill_a));
-            e->spill_elems = total;
-            HIP_CHECK(hipMalloc(&e->d_spill_k, 8 * total));
-            HIP_CHECK(hipMalloc(&e->d_spill_a, 8 * total));
-        }
+        e->d_spill_k.reserve(total);
+        e->d_spill_a.reserve(total);
     }
 
     HIP_CHECK(hipStreamSynchronize(st));
@@ -1998,8 +2011,8 @@ static void run_halo1a(mv_engine *e, const i64 *commArr, ncclComm_t comm,
     k8_gather_comms<<<grid_for(std::max<i64>(e->ssz, 1)), 256, 0, st2>>>(
         e->ssz, e->d_svdata_int, commArr, e->d_scdata);
     if (!e->use_delta) {
-        rccl_alltoallv(e, e->d_scdata, e->send_off.data(), e->d_ghost_labels,
-                       e->recv_off.data(), 8, ncclInt64, 8, comm, st2);
+        alltoallv(e, e->d_scdata, e->send_off.data(), e->d_ghost_labels,
+                  e->recv_off.data(), 8, ncclInt64, comm, st2);
     } else {
         HIP_CHECK(hipMemsetAsync(e->d_chg_cnt, 0, 8 * p, st2));
         k_delta_compact<<<grid_for(std::max<i64>(e->ssz, 1)), 256, 0, st2>>>(
@@ -2008,93 +2021,35 @@ static void run_halo1a(mv_engine *e, const i64 *commArr, ncclComm_t comm,
         // tiny count matrix; rides the same stream/comm so it overlaps the
         // interior sweep in overlap mode (the host blocks only on these
         // small ops — the interior sweep is already issued)
-        if (e->lb) {
-            std::vector<i64> mine(p), m;
-            HIP_CHECK(hipMemcpyAsync(mine.data(), (i64 *)e->d_chg_cnt, 8 * p,
-                                     hipMemcpyDeviceToHost, st2));
-            HIP_CHECK(hipStreamSynchronize(st2));
-            exchange_counts(e, mine, m, comm, st2);
-            std::copy(m.begin(), m.end(), e->h_cntmat);
-        } else {
-            HIP_CHECK(hipMemcpyAsync(e->d_cntmat + (i64)e->rank * p,
-                                     e->d_chg_cnt, 8 * p,
-                                     hipMemcpyDeviceToDevice, st2));
-            NCCL_CHECK(ncclAllGather(e->d_cntmat + (i64)e->rank * p,
-                                     e->d_cntmat, p, ncclInt64, comm, st2));
-            HIP_CHECK(hipMemcpyAsync(e->h_cntmat, e->d_cntmat, 8 * p * p,
-                                     hipMemcpyDeviceToHost, st2));
-            HIP_CHECK(hipStreamSynchronize(st2));
-        }
+        allgather_counts(e, (const i64 *)e->d_chg_cnt.get(),
+                         /*on_device*/ true, e->h_cntmat, comm, st2);
         // mixed full/compact payload: both ends of every pair decide from
         // the same matrix entry, so the plan is symmetric by construction
         auto full_mode = [](i64 changed, i64 seg) {
             return changed * 12 >= seg * 8;
         };
-        if (e->lb) {
-            mv_lb_session *s = e->lb;
-            HIP_CHECK(hipStreamSynchronize(st2));
-            s->posts[e->rank].send = e->d_scdata;
-            s->posts[e->rank].send2 = e->d_chg_idx;
-            s->posts[e->rank].send3 = e->d_chg_lab;
-            s->posts[e->rank].soff = e->send_off.data();
-            s->barrier();
-            for (int r = 0; r < p; r++) {
-                if (r == e->rank) continue;
-                const auto &ps = s->posts[r];
-                const i64 seg = e->recv_off[r + 1] - e->recv_off[r];
-                const i64 chg = e->h_cntmat[(i64)r * p + e->rank];
-                const i64 sb = ps.soff[e->rank];
-                if (full_mode(chg, seg)) {
-                    if (seg > 0)
-                        HIP_CHECK(hipMemcpyAsync(
-                            e->d_ghost_labels + e->recv_off[r],
-                            (const i64 *)ps.send + sb, 8 * seg,
-                            hipMemcpyDeviceToDevice, st2));
-                } else if (chg > 0) {
-                    HIP_CHECK(hipMemcpyAsync(
-                        e->d_rchg_idx + e->recv_off[r],
-                        (const unsigned *)ps.send2 + sb, 4 * chg,
-                        hipMemcpyDeviceToDevice, st2));
-                    HIP_CHECK(hipMemcpyAsync(
-                        e->d_rchg_lab + e->recv_off[r],
-                        (const i64 *)ps.send3 + sb, 8 * chg,
-                        hipMemcpyDeviceToDevice, st2));
-                }
+        // one direction of the plan for peer r: the whole segment, or the
+        // (chg_idx, chg_lab) pair of its changed entries, or nothing
+        auto plan = [&](std::vector<Xfer> &out, int r, i64 off, i64 seg,
+                        i64 chg, i64 *full, unsigned *idx, i64 *lab) {
+            if (full_mode(chg, seg)) {
+                if (seg > 0) out.push_back({r, full + off, ncclInt64, seg});
+            } else if (chg > 0) {
+                out.push_back({r, idx + off, ncclChar, chg * 4});
+                out.push_back({r, lab + off, ncclInt64, chg});
             }
-            HIP_CHECK(hipStreamSynchronize(st2));
-            s->barrier();
-        } else {
-            NCCL_CHECK(ncclGroupStart());
-            for (int r = 0; r < p; r++) {
-                if (r == e->rank) continue;
-                const i64 sseg = e->send_off[r + 1] - e->send_off[r];
-                const i64 schg = e->h_cntmat[(i64)e->rank * p + r];
-                if (full_mode(schg, sseg)) {
-                    if (sseg > 0)
-                        NCCL_CHECK(ncclSend(e->d_scdata + e->send_off[r],
-                                            sseg, ncclInt64, r, comm, st2));
-                } else if (schg > 0) {
-                    NCCL_CHECK(ncclSend(e->d_chg_idx + e->send_off[r],
-                                        schg * 4, ncclChar, r, comm, st2));
-                    NCCL_CHECK(ncclSend(e->d_chg_lab + e->send_off[r],
-                                        schg, ncclInt64, r, comm, st2));
-                }
-                const i64 rseg = e->recv_off[r + 1] - e->recv_off[r];
-                const i64 rchg = e->h_cntmat[(i64)r * p + e->rank];
-                if (full_mode(rchg, rseg)) {
-                    if (rseg > 0)
-                        NCCL_CHECK(
-                            ncclRecv(e->d_ghost_labels + e->recv_off[r],
-                                     rseg, ncclInt64, r, comm, st2));
-                } else if (rchg > 0) {
-                    NCCL_CHECK(ncclRecv(e->d_rchg_idx + e->recv_off[r],
-                                        rchg * 4, ncclChar, r, comm, st2));
-                    NCCL_CHECK(ncclRecv(e->d_rchg_lab + e->recv_off[r],
-                                        rchg, ncclInt64, r, comm, st2));
-                }
-            }
-            NCCL_CHECK(ncclGroupEnd());
+        };
+        std::vector<Xfer> sends, recvs;
+        for (int r = 0; r < p; r++) {
+            if (r == e->rank) continue;
+            plan(sends, r, e->send_off[r], e->send_off[r + 1] - e->send_off[r],
+                 e->h_cntmat[(i64)e->rank * p + r], e->d_scdata, e->d_chg_idx,
+                 e->d_chg_lab);
+            plan(recvs, r, e->recv_off[r], e->recv_off[r + 1] - e->recv_off[r],
+                 e->h_cntmat[(i64)r * p + e->rank], e->d_ghost_labels,
+                 e->d_rchg_idx, e->d_rchg_lab);
         }
+        exchange(e, sends, recvs, comm, st2);
         for (int r = 0; r < p; r++) { // scatter compact segments
             if (r == e->rank) continue;
             const i64 rseg = e->recv_off[r + 1] - e->recv_off[r];
@@ -2124,31 +2079,21 @@ static void halo_prep(mv_engine *e, const i64 *curr,
     const i64 lnv = e->lnv;
     // ---- needed remote communities (dspl.hpp:670-700) ----
     const i64 cand_max = e->nghost + lnv;
-    if (cand_max > e->rc_cap) {
-        for (void *q : {(void *)e->d_cand, (void *)e->d_cand_sorted,
-                        (void *)e->d_rc_ids, (void *)e->d_rc_info,
-                        (void *)e->d_rcu})
-            if (q) HIP_CHECK(hipFree(q));
-        e->rc_cap = cand_max;
-        HIP_CHECK(hipMalloc(&e->d_cand, 8 * cand_max));
-        HIP_CHECK(hipMalloc(&e->d_cand_sorted, 8 * cand_max));
-        HIP_CHECK(hipMalloc(&e->d_rc_ids, 8 * cand_max));
-        HIP_CHECK(hipMalloc(&e->d_rc_info, sizeof(Info16) * cand_max));
-        HIP_CHECK(hipMalloc(&e->d_rcu, sizeof(Info16) * cand_max));
+    if (e->d_cand.reserve(cand_max)) { // first call after a load
+        e->d_cand_sorted.reserve(cand_max);
+        e->d_rc_ids.reserve(cand_max);
+        e->d_rc_info.reserve(cand_max);
+        e->d_rcu.reserve(cand_max);
         size_t t1 = 0, t2 = 0;
-        (void)hipcub::DeviceRadixSort::SortKeys(nullptr, t1, e->d_cand,
-                                                e->d_cand_sorted, cand_max,
-                                                0, e->sort_bits, st2);
+        (void)hipcub::DeviceRadixSort::SortKeys(
+            nullptr, t1, e->d_cand.get(), e->d_cand_sorted.get(), cand_max, 0,
+            e->sort_bits, st2);
         i64 *dummy = nullptr;
-        (void)hipcub::DeviceSelect::Unique(nullptr, t2, e->d_cand_sorted,
-                                           e->d_rc_ids, dummy, cand_max,
+        (void)hipcub::DeviceSelect::Unique(nullptr, t2,
+                                           e->d_cand_sorted.get(),
+                                           e->d_rc_ids.get(), dummy, cand_max,
                                            st2);
-        size_t need = std::max(t1, t2);
-        if (need > e->cub_tmp_bytes) {
-            if (e->d_cub_tmp) HIP_CHECK(hipFree(e->d_cub_tmp));
-            HIP_CHECK(hipMalloc(&e->d_cub_tmp, need));
-            e->cub_tmp_bytes = need;
-        }
+        e->d_cub_tmp.reserve((i64)std::max(t1, t2));
     }
     HIP_CHECK(hipMemsetAsync(e->d_count, 0, 8, st2));
     k_filter_remote<<<grid_for(std::max<i64>(e->nghost, 1)), 256, 0, st2>>>(
@@ -2160,15 +2105,16 @@ static void halo_prep(mv_engine *e, const i64 *curr,
     HIP_CHECK(hipMemcpyAsync(&ncand, e->d_count, 8, hipMemcpyDeviceToHost,
                              st2));
     HIP_CHECK(hipStreamSynchronize(st2));
-    size_t tb = e->cub_tmp_bytes;
-    (void)hipcub::DeviceRadixSort::SortKeys(e->d_cub_tmp, tb, e->d_cand,
-                                            e->d_cand_sorted, (int64_t)ncand,
-                                            0, e->sort_bits, st2);
-    i64 *d_nrc = (i64 *)e->d_count; // reuse as output slot
-    tb = e->cub_tmp_bytes;
-    (void)hipcub::DeviceSelect::Unique(e->d_cub_tmp, tb, e->d_cand_sorted,
-                                       e->d_rc_ids, d_nrc, (int64_t)ncand,
-                                       st2);
+    size_t tb = (size_t)e->d_cub_tmp.cap;
+    (void)hipcub::DeviceRadixSort::SortKeys(
+        e->d_cub_tmp.get(), tb, e->d_cand.get(), e->d_cand_sorted.get(),
+        (int64_t)ncand, 0, e->sort_bits, st2);
+    i64 *d_nrc = (i64 *)e->d_count.get(); // reuse as output slot
+    tb = (size_t)e->d_cub_tmp.cap;
+    (void)hipcub::DeviceSelect::Unique(e->d_cub_tmp.get(), tb,
+                                       e->d_cand_sorted.get(),
+                                       e->d_rc_ids.get(), d_nrc,
+                                       (int64_t)ncand, st2);
     i64 nrc = 0;
     HIP_CHECK(hipMemcpyAsync(&nrc, d_nrc, 8, hipMemcpyDeviceToHost, st2));
     HIP_CHECK(hipStreamSynchronize(st2));
@@ -2181,31 +2127,30 @@ static void halo_prep(mv_engine *e, const i64 *curr,
     HIP_CHECK(hipMemcpyAsync(rc_bounds.data(), e->d_bounds, 8 * (p + 1),
                              hipMemcpyDeviceToHost, st2));
     HIP_CHECK(hipStreamSynchronize(st2));
-    std::vector<i64> reqs(p), matrix;
+    std::vector<i64> reqs(p), matrix((size_t)p * p);
     for (int r = 0; r < p; r++) reqs[r] = rc_bounds[r + 1] - rc_bounds[r];
-    exchange_counts(e, reqs, matrix, comm, st2);
+    allgather_counts(e, reqs.data(), /*on_device*/ false, matrix.data(), comm,
+                     st2);
     req_off.assign(p + 1, 0);
     for (int r = 0; r < p; r++)
         req_off[r + 1] =
             req_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
     const i64 nreq = req_off[p];
-    if (nreq > e->req_cap) { // rare growth; device-wide hipFree sync is ok
-        if (e->d_req_ids) HIP_CHECK(hipFree(e->d_req_ids));
-        if (e->d_req_info) HIP_CHECK(hipFree(e->d_req_info));
-        e->req_cap = std::max<i64>(nreq, 64);
-        HIP_CHECK(hipMalloc(&e->d_req_ids, 8 * e->req_cap));
-        HIP_CHECK(hipMalloc(&e->d_req_info, sizeof(Info16) * e->req_cap));
+    if (nreq > e->d_req_ids.cap) { // rare growth; device-wide hipFree sync
+                                   // is ok
+        e->d_req_ids.reserve(std::max<i64>(nreq, 64));
+        e->d_req_info.reserve(std::max<i64>(nreq, 64));
     }
     // the previous iteration's delta routing reads d_req_ids/d_req_info
     // and writes cinfo; #1c's recv and the replies must order after it
     if (ev_cinfo) HIP_CHECK(hipStreamWaitEvent(st2, ev_cinfo, 0));
-    rccl_alltoallv(e, e->d_rc_ids, rc_bounds.data(), e->d_req_ids,
-                   req_off.data(), 8, ncclInt64, 8, comm, st2);
+    alltoallv(e, e->d_rc_ids, rc_bounds.data(), e->d_req_ids, req_off.data(),
+              8, ncclInt64, comm, st2);
     k9_reply_info<<<grid_for(std::max<i64>(nreq, 1)), 256, 0, st2>>>(
         nreq, e->d_req_ids, e->base, e->d_sigma_inv, e->d_cinfo,
         e->d_req_info);
-    rccl_alltoallv(e, e->d_req_info, req_off.data(), e->d_rc_info,
-                   rc_bounds.data(), sizeof(Info16), ncclChar, 1, comm, st2);
+    alltoallv(e, e->d_req_info, req_off.data(), e->d_rc_info,
+              rc_bounds.data(), sizeof(Info16), ncclChar, comm, st2);
     HIP_CHECK(hipMemsetAsync(e->d_rcu, 0,
                              sizeof(Info16) * std::max<i64>(nrc, 1), st2));
     // u32 views for the sweep (slot / lnv + rc index encoding)
@@ -2216,6 +2161,117 @@ static void halo_prep(mv_engine *e, const i64 *curr,
         e->nghost, e->d_ghost_labels, e->base, e->bound, lnv,
         e->d_sigma_inv, e->d_rc_ids, nrc, e->d_vghost);
     nrc_out = nrc;
+}
+
+// exchangeVertexReqs equivalent (dspl.hpp:1112-1272), the head of the
+// timed setup span: ghost discovery, the want-list exchange, the export /
+// delta state, the SELL image (p>1) and the global overlap decision.
+static void exchange_vertex_reqs(mv_engine *e) {
+    hipStream_t st = e->stream;
+    const i64 lnv = e->lnv, lne = e->lne;
+    const int p = e->nranks, me = e->rank;
+    HIP_CHECK(hipMemsetAsync(e->d_count, 0, 8, st));
+    if (p == 1) {
+        e->nghost = 0;
+        e->ssz = 0;
+        return; // the SELL image was built at load
+    }
+    {
+        DevBuf<i64> d_rem, d_sorted, d_ng; // temporaries: freed with this
+        DevBuf<char> d_tmp;                // block
+        d_rem.reserve(lne);
+        k_select_remote<<<grid_for(lne), 256, 0, st>>>(
+            lne, e->d_tails, e->base, e->bound, d_rem, e->d_count);
+        unsigned long long nrem = 0;
+        HIP_CHECK(hipMemcpyAsync(&nrem, e->d_count, 8, hipMemcpyDeviceToHost,
+                                 st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        // sort + unique -> ghosts
+        d_sorted.reserve((i64)nrem);
+        e->d_ghosts.reserve((i64)nrem);
+        d_ng.reserve(1);
+        size_t tmp1 = 0, tmp2 = 0;
+        (void)hipcub::DeviceRadixSort::SortKeys(
+            nullptr, tmp1, d_rem.get(), d_sorted.get(), (int64_t)nrem, 0,
+            e->sort_bits, st);
+        (void)hipcub::DeviceSelect::Unique(nullptr, tmp2, d_sorted.get(),
+                                           e->d_ghosts.get(), d_ng.get(),
+                                           (int64_t)nrem, st);
+        d_tmp.reserve((i64)std::max(tmp1, tmp2));
+        (void)hipcub::DeviceRadixSort::SortKeys(
+            d_tmp.get(), tmp1, d_rem.get(), d_sorted.get(), (int64_t)nrem, 0,
+            e->sort_bits, st);
+        (void)hipcub::DeviceSelect::Unique(d_tmp.get(), tmp2, d_sorted.get(),
+                                           e->d_ghosts.get(), d_ng.get(),
+                                           (int64_t)nrem, st);
+        HIP_CHECK(hipMemcpyAsync(&e->nghost, d_ng, 8, hipMemcpyDeviceToHost,
+                                 st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    // per-owner segments of my (sorted) want list
+    k_owner_bounds<<<1, p + 1, 0, st>>>(e->d_ghosts, e->nghost, e->d_parts, p,
+                                        e->d_bounds);
+    e->recv_off.resize(p + 1);
+    HIP_CHECK(hipMemcpyAsync(e->recv_off.data(), e->d_bounds, 8 * (p + 1),
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+
+    // exchange want-list sizes, then the lists (dspl.hpp:1184-1252)
+    std::vector<i64> want(p), matrix((size_t)p * p);
+    for (int r = 0; r < p; r++) want[r] = e->recv_off[r + 1] - e->recv_off[r];
+    allgather_counts(e, want.data(), /*on_device*/ false, matrix.data(),
+                     e->comm, st);
+    e->send_off.assign(p + 1, 0);
+    for (int r = 0; r < p; r++)
+        e->send_off[r + 1] =
+            e->send_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
+    e->ssz = e->send_off[p];
+    e->d_svdata.reserve(e->ssz);
+    e->d_svdata_int.reserve(e->ssz);
+    // role swap (dspl.hpp:1255-1257): my ghost list goes OUT, the peers'
+    // lists land in svdata
+    alltoallv(e, e->d_ghosts, e->recv_off.data(), e->d_svdata,
+              e->send_off.data(), 8, ncclInt64, e->comm, st);
+    k_to_internal<<<grid_for(std::max<i64>(e->ssz, 1)), 256, 0, st>>>(
+        e->ssz, e->d_svdata, e->base, e->d_sigma_inv, e->d_svdata_int);
+    HIP_CHECK(hipStreamSynchronize(st));
+
+    e->d_vghost.reserve(e->nghost);
+    e->d_vcurr.reserve(lnv);
+    e->d_vtarget.reserve(lnv);
+    e->d_scdata.reserve(e->ssz);
+
+    // delta-compaction state (default on; MV_NO_DELTA reverts to the
+    // reference's full resend for A/B). The buffers are reused across
+    // runs; every run starts from "all changed" (d_last_sent = -1), so
+    // iteration 1 resends every segment in full and nothing reads what a
+    // previous run left in the others.
+    e->use_delta = !getenv("MV_NO_DELTA");
+    e->d_last_sent.reserve(e->ssz);
+    HIP_CHECK(hipMemsetAsync(e->d_last_sent, 0xFF,
+                             8 * std::max<i64>(e->ssz, 1), st));
+    e->d_chg_idx.reserve(e->ssz);
+    e->d_chg_lab.reserve(e->ssz);
+    e->d_chg_cnt.reserve(p);
+    e->d_soff.reserve(p + 1);
+    HIP_CHECK(hipMemcpyAsync(e->d_soff, e->send_off.data(), 8 * (p + 1),
+                             hipMemcpyHostToDevice, st));
+    e->d_ghost_labels.reserve(e->nghost);
+    e->d_rchg_idx.reserve(e->nghost);
+    e->d_rchg_lab.reserve(e->nghost);
+    e->h_cntmat.reserve((i64)p * p);
+    HIP_CHECK(hipStreamSynchronize(st));
+
+    build_sell(e);
+    // overlap changes the collective sequence, so it must be a GLOBAL
+    // decision: all ranks take it or none (a rank can be locally skewed /
+    // export-free while others are not)
+    std::vector<i64> flag(p, e->overlap ? 1 : 0);
+    allgather_counts(e, flag.data(), /*on_device*/ false, matrix.data(),
+                     e->comm, st);
+    for (int r = 0; r < p; r++)
+        if (matrix[(size_t)r * p] == 0) e->overlap = 0;
 }
 
 #define PHASE(tag)                                                            \
@@ -2233,140 +2289,13 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     const auto t_start = std::chrono::steady_clock::now();
     hipStream_t st = e->stream;
     const i64 lnv = e->lnv, lne = e->lne;
-    const int p = e->nranks, me = e->rank;
+    const int p = e->nranks;
     e->ev_used = 0;
     e->stats = mv_stats{};
     e->stats.edges_local = lne;
 
-    // ---- exchangeVertexReqs equivalent (dspl.hpp:1112-1272) ----
     const auto t_setup0 = std::chrono::steady_clock::now();
-    {
-        HIP_CHECK(hipMemsetAsync(e->d_count, 0, 8, st));
-        if (p > 1) {
-            i64 *d_rem = nullptr;
-            HIP_CHECK(hipMalloc(&d_rem, 8 * std::max<i64>(lne, 1)));
-            k_select_remote<<<grid_for(lne), 256, 0, st>>>(
-                lne, e->d_tails, e->base, e->bound, d_rem, e->d_count);
-            unsigned long long nrem = 0;
-            HIP_CHECK(hipMemcpyAsync(&nrem, e->d_count, 8,
-                                     hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            // sort + unique -> ghosts
-            i64 *d_sorted = nullptr;
-            HIP_CHECK(hipMalloc(&d_sorted, 8 * std::max<i64>((i64)nrem, 1)));
-            if (!e->d_ghosts)
-                HIP_CHECK(hipMalloc(&e->d_ghosts,
-                                    8 * std::max<i64>((i64)nrem, 1)));
-            size_t tmp1 = 0, tmp2 = 0;
-            (void)hipcub::DeviceRadixSort::SortKeys(nullptr, tmp1, d_rem, d_sorted,
-                                              (int64_t)nrem, 0, e->sort_bits,
-                                              st);
-            i64 *d_ng = nullptr;
-            HIP_CHECK(hipMalloc(&d_ng, 8));
-            (void)hipcub::DeviceSelect::Unique(nullptr, tmp2, d_sorted, e->d_ghosts,
-                                         d_ng, (int64_t)nrem, st);
-            size_t tmpb = std::max(tmp1, tmp2);
-            void *d_tmp = nullptr;
-            HIP_CHECK(hipMalloc(&d_tmp, std::max<size_t>(tmpb, 1)));
-            (void)hipcub::DeviceRadixSort::SortKeys(d_tmp, tmp1, d_rem, d_sorted,
-                                              (int64_t)nrem, 0, e->sort_bits,
-                                              st);
-            (void)hipcub::DeviceSelect::Unique(d_tmp, tmp2, d_sorted, e->d_ghosts,
-                                         d_ng, (int64_t)nrem, st);
-            HIP_CHECK(hipMemcpyAsync(&e->nghost, d_ng, 8,
-                                     hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            HIP_CHECK(hipFree(d_rem));
-            HIP_CHECK(hipFree(d_sorted));
-            HIP_CHECK(hipFree(d_ng));
-            HIP_CHECK(hipFree(d_tmp));
-
-            // per-owner segments of my (sorted) want list
-            k_owner_bounds<<<1, p + 1, 0, st>>>(e->d_ghosts, e->nghost,
-                                                e->d_parts, p, e->d_bounds);
-            e->recv_off.resize(p + 1);
-            HIP_CHECK(hipMemcpyAsync(e->recv_off.data(), e->d_bounds,
-                                     8 * (p + 1), hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-
-            // exchange want-list sizes, then the lists (dspl.hpp:1184-1252)
-            std::vector<i64> want(p), matrix;
-            for (int r = 0; r < p; r++)
-                want[r] = e->recv_off[r + 1] - e->recv_off[r];
-            exchange_counts(e, want, matrix, e->comm, e->stream);
-            e->send_off.assign(p + 1, 0);
-            for (int r = 0; r < p; r++)
-                e->send_off[r + 1] =
-                    e->send_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
-            e->ssz = e->send_off[p];
-            if (e->d_svdata) HIP_CHECK(hipFree(e->d_svdata));
-            if (e->d_svdata_int) HIP_CHECK(hipFree(e->d_svdata_int));
-            HIP_CHECK(hipMalloc(&e->d_svdata, 8 * std::max<i64>(e->ssz, 1)));
-            HIP_CHECK(hipMalloc(&e->d_svdata_int,
-                                4 * std::max<i64>(e->ssz, 1)));
-            // role swap (dspl.hpp:1255-1257): my ghost list goes OUT, the
-            // peers' lists land in svdata
-            rccl_alltoallv(e, e->d_ghosts, e->recv_off.data(), e->d_svdata,
-                           e->send_off.data(), 8, ncclInt64, 8, e->comm,
-                           e->stream);
-            k_to_internal<<<grid_for(std::max<i64>(e->ssz, 1)), 256, 0, st>>>(
-                e->ssz, e->d_svdata, e->base, e->d_sigma_inv, e->d_svdata_int);
-            HIP_CHECK(hipStreamSynchronize(st));
-
-            if (e->d_vghost) HIP_CHECK(hipFree(e->d_vghost));
-            HIP_CHECK(hipMalloc(&e->d_vghost,
-                                4 * std::max<i64>(e->nghost, 1)));
-            if (!e->d_vcurr) HIP_CHECK(hipMalloc(&e->d_vcurr, 4 * lnv));
-            if (!e->d_vtarget) HIP_CHECK(hipMalloc(&e->d_vtarget, 4 * lnv));
-            if (e->d_scdata) HIP_CHECK(hipFree(e->d_scdata));
-            HIP_CHECK(hipMalloc(&e->d_scdata, 8 * std::max<i64>(e->ssz, 1)));
-
-            // delta-compaction state (default on; MV_NO_DELTA reverts to
-            // the reference's full resend for A/B)
-            e->use_delta = !getenv("MV_NO_DELTA");
-            const i64 sszc = std::max<i64>(e->ssz, 1);
-            const i64 ngc = std::max<i64>(e->nghost, 1);
-            for (void **q :
-                 {(void **)&e->d_last_sent, (void **)&e->d_chg_idx,
-                  (void **)&e->d_chg_lab, (void **)&e->d_chg_cnt,
-                  (void **)&e->d_cntmat, (void **)&e->d_soff,
-                  (void **)&e->d_ghost_labels, (void **)&e->d_rchg_idx,
-                  (void **)&e->d_rchg_lab})
-                if (*q) {
-                    HIP_CHECK(hipFree(*q));
-                    *q = nullptr;
-                }
-            HIP_CHECK(hipMalloc(&e->d_last_sent, 8 * sszc));
-            HIP_CHECK(hipMemsetAsync(e->d_last_sent, 0xFF, 8 * sszc, st));
-            HIP_CHECK(hipMalloc(&e->d_chg_idx, 4 * sszc));
-            HIP_CHECK(hipMalloc(&e->d_chg_lab, 8 * sszc));
-            HIP_CHECK(hipMalloc(&e->d_chg_cnt, 8 * p));
-            HIP_CHECK(hipMalloc(&e->d_cntmat, 8 * p * p));
-            HIP_CHECK(hipMalloc(&e->d_soff, 8 * (p + 1)));
-            HIP_CHECK(hipMemcpyAsync(e->d_soff, e->send_off.data(),
-                                     8 * (p + 1), hipMemcpyHostToDevice, st));
-            HIP_CHECK(hipMalloc(&e->d_ghost_labels, 8 * ngc));
-            HIP_CHECK(hipMalloc(&e->d_rchg_idx, 4 * ngc));
-            HIP_CHECK(hipMalloc(&e->d_rchg_lab, 8 * ngc));
-            if (!e->h_cntmat)
-                HIP_CHECK(hipHostMalloc(&e->h_cntmat, 8 * p * p));
-            HIP_CHECK(hipStreamSynchronize(st));
-        } else {
-            e->nghost = 0;
-            e->ssz = 0;
-        }
-
-        if (p > 1) {
-            build_sell(e); // p==1: built at load
-            // overlap changes the collective sequence, so it must be a
-            // GLOBAL decision: all ranks take it or none (a rank can be
-            // locally skewed / export-free while others are not)
-            std::vector<i64> flag(p, e->overlap ? 1 : 0), fm;
-            exchange_counts(e, flag, fm, e->comm, e->stream);
-            for (int r = 0; r < p; r++)
-                if (fm[(size_t)r * p] == 0) e->overlap = 0;
-        }
-    }
+    exchange_vertex_reqs(e);
 
     PHASE("setup-done");
     // ---- distInitLouvain (dspl.hpp:151-172) ----
@@ -2376,7 +2305,8 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     PHASE("k1-done");
     const int nblocks = grid_for(lnv);
     {
-        auto f = [vd = e->d_vdeg] __device__(i64 i, double &a, double &b) {
+        auto f = [vd = e->d_vdeg.get()] __device__(i64 i, double &a,
+                                                   double &b) {
             a = vd[i];
             b = 0.0;
         };
@@ -2394,7 +2324,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     PHASE("k2-done");
     if (p == 1) // slot mode: the i64 arrays alias u32 slot arrays
         k3_init_comm32<<<grid_for(lnv), 256, 0, st>>>(
-            lnv, (unsigned *)e->d_curr, (unsigned *)e->d_past);
+            lnv, (unsigned *)e->d_curr.get(), (unsigned *)e->d_past.get());
     else
         k3_init_comm<<<grid_for(lnv), 256, 0, st>>>(lnv, e->base, e->d_sigma,
                                                     e->d_curr, e->d_past);
@@ -2518,7 +2448,8 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                     e->d_vghost, e->d_vdeg, e->d_sigma, e->d_cinfo,
                     e->d_cupd, e->d_rc_ids, e->d_rc_info, e->d_rcu,
                     constant, vtarget, e->d_cw,
-                    (unsigned *)e->d_spill_k, e->d_spill_a, e->d_spill_off);
+                    (unsigned *)e->d_spill_k.get(), e->d_spill_a,
+                    e->d_spill_off);
         };
         auto dispatch_slots = [&](auto mr_tag, auto unit_tag, i64 s0,
                                   i64 s1) {
@@ -2638,9 +2569,9 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         // ---- halo #2: route deltas to owners (dspl.hpp:978-1103) ----
         if (p > 1) {
             const auto t_h0 = std::chrono::steady_clock::now();
-            rccl_alltoallv(e, e->d_rcu, rc_bounds.data(), e->d_req_info,
-                           req_off.data(), sizeof(Info16), ncclChar, 1,
-                           e->comm, e->stream);
+            alltoallv(e, e->d_rcu, rc_bounds.data(), e->d_req_info,
+                      req_off.data(), sizeof(Info16), ncclChar, e->comm,
+                      e->stream);
             // apply per SENDER segment, in rank order: same-stream launches
             // serialize, and one sender's ids are unique (sorted rc_ids), so
             // cinfo degree bits are run-to-run identical at any nranks —
@@ -2668,7 +2599,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         // ---- K7: modularity (dspl.hpp:407-456; p==1 already emitted the
         // partials in the fused kernel above) ----
         if (p > 1) {
-            auto f = [cw = e->d_cw, ci = e->d_cinfo] __device__(
+            auto f = [cw = e->d_cw.get(), ci = e->d_cinfo.get()] __device__(
                          i64 i, double &a, double &b) {
                 a = cw[i];
                 const double d = ci[i].degree;

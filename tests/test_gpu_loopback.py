@@ -57,6 +57,47 @@ def _run_loopback(nv, world, unit=True, trace_cap=64):
     return results
 
 
+def _run_loopback_sequence(world, loads, runs_per_load=1, trace_cap=64):
+    """One engine per rank, kept alive across `loads` (a list of RGG sizes,
+    each loaded in turn on the SAME engine) with `runs_per_load` runs after
+    every load. Returns one _run_loopback-shaped result dict per run."""
+    from minivite_amd import Graph, Engine, LoopbackSession
+    ses = LoopbackSession(world)
+    nruns = len(loads) * runs_per_load
+    results = [dict() for _ in range(nruns)]
+    errors = []
+
+    def rank_main(r):
+        try:
+            e = Engine.loopback(ses, r, device=0)
+            k = 0
+            for nv in loads:
+                g = Graph.rgg(nv, r, world, unit_weight=True)
+                e.load_graph(g)
+                e.set_trace(trace_cap)
+                for _ in range(runs_per_load):
+                    mod, iters = e.run()
+                    tt, tm = e.trace(iters)
+                    results[k][r] = (mod, iters, tt.copy(),
+                                     [float(m).hex() for m in tm])
+                    k += 1
+                g.free()
+            e.destroy()
+        except Exception as ex:  # pragma: no cover
+            errors.append((r, repr(ex)))
+
+    threads = [threading.Thread(target=rank_main, args=(r,))
+               for r in range(world)]
+    for t in threads:
+        t.start()
+    for t in threads:
+        t.join(timeout=600)
+    ses.destroy()
+    assert not errors, errors
+    assert all(len(res) == world for res in results)
+    return results
+
+
 def _check_vs_pin(results, pin, world, exact_mod=True):
     from oracle.oracle import sha
     nv = pin["nv"]
@@ -93,6 +134,28 @@ def test_loopback_parity_p8_n32768():
     pin = pins["rgg_n32768_p8_unit"]
     results = _run_loopback(32768, 8, unit=True)
     _check_vs_pin(results, pin, 8, exact_mod=True)
+
+
+def test_loopback_rerun_p2():
+    """Two run() calls on the same loaded engines (p=2): the second run
+    reuses the ghost / export / delta buffers the first one sized and must
+    re-initialise them (last-sent labels back to "all changed"), so both
+    runs match the pin bit-for-bit."""
+    pins = json.load(open(GOLDEN))
+    pin = pins["rgg_n16384_p2_unit"]
+    for results in _run_loopback_sequence(2, [16384], runs_per_load=2):
+        _check_vs_pin(results, pin, 2, exact_mod=True)
+
+
+def test_loopback_reload_grow_shrink_p4():
+    """load_graph on live engines (p=4): a larger graph, then the first
+    one again. Every per-graph buffer and size must follow the load — no
+    stale capacity, ghost count or trace buffer from the previous graph."""
+    pins = json.load(open(GOLDEN))
+    sizes = [16384, 65536, 16384]
+    runs = _run_loopback_sequence(4, sizes)
+    for nv, results in zip(sizes, runs):
+        _check_vs_pin(results, pins[f"rgg_n{nv}_p4_unit"], 4, exact_mod=True)
 
 
 def test_loopback_parity_weighted_p2():
@@ -158,7 +221,9 @@ def _zipf_graph(nv, max_deg, seed=7, weighted=False):
 def test_loopback_skewed_p2(weighted):
     """Skewed (hub-heavy) graph partitioned 2 ways: exercises the
     multi-rank wave-per-vertex hub kernel (unit) / the spill path (-w)
-    under the view encoding; engine vs oracle on identical CSRs."""
+    under the view encoding; engine vs oracle on identical CSRs. Each
+    rank runs twice on the same engine: the second run rebuilds the
+    hash-band offsets and reuses the band buffers."""
     from minivite_amd import Graph, Engine, LoopbackSession
     from oracle.oracle import OracleGraph, louvain, sha
     nv, world = 50000, 2
@@ -177,7 +242,7 @@ def test_loopback_skewed_p2(weighted):
     og.free()
 
     ses = LoopbackSession(world)
-    results = {}
+    runs = [dict(), dict()]
     errors = []
 
     def rank_main(r):
@@ -187,15 +252,15 @@ def test_loopback_skewed_p2(weighted):
             e = Engine.loopback(ses, r, device=0)
             e.load_graph(g)
             e.set_trace(300)
-            mod, iters = e.run()
-            tt, _ = e.trace(iters)
-            results[r] = (mod, iters, tt.copy())
+            for results in runs:
+                mod, iters = e.run()
+                tt, _ = e.trace(iters)
+                results[r] = (mod, iters, tt.copy())
             e.destroy()
             g.free()
         except Exception as ex:  # pragma: no cover
             errors.append((r, repr(ex)))
 
-    import threading
     threads = [threading.Thread(target=rank_main, args=(r,))
                for r in range(world)]
     for t in threads:
@@ -204,17 +269,21 @@ def test_loopback_skewed_p2(weighted):
         t.join(timeout=600)
     ses.destroy()
     assert not errors, errors
-    iters = results[0][1]
-    assert iters == oiters
-    if weighted:
-        assert abs(results[0][0] - omod) < 1e-9
-    else:
-        assert float(results[0][0]).hex() == float(omod).hex()
-    for k in range(min(iters, 300)):
-        full = np.zeros(nv, dtype=np.int64)
-        for r in range(world):
-            full[parts[r]:parts[r + 1]] = results[r][2][k]
-        assert sha(full) == sha(ott[k]), f"iteration {k+1}"
+    osha = [sha(ott[k]) for k in range(min(oiters, 300))]
+    for n, results in enumerate(runs):
+        assert len(results) == world, f"run {n+1}"
+        iters = results[0][1]
+        assert iters == oiters, f"run {n+1}"
+        if weighted:
+            assert abs(results[0][0] - omod) < 1e-9, f"run {n+1}"
+        else:
+            assert float(results[0][0]).hex() == float(omod).hex(), \
+                f"run {n+1}"
+        for k in range(min(iters, 300)):
+            full = np.zeros(nv, dtype=np.int64)
+            for r in range(world):
+                full[parts[r]:parts[r + 1]] = results[r][2][k]
+            assert sha(full) == osha[k], f"run {n+1} iteration {k+1}"
 
 
 def test_loopback_balanced_read_p4():
