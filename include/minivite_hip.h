@@ -137,6 +137,78 @@ typedef struct {
 } mv_stats;
 void mv_engine_get_stats(const mv_engine *e, mv_stats *out);
 
+/* ---- beyond phase one: assignment, aggregation, multi-phase driver ----
+ * The reference mini-app stops after one phase and never hands the
+ * assignment out (main.cpp:164-196 prints modularity and iterations only);
+ * unless noted, the entries below have no counterpart there. Definitions:
+ * DESIGN.md, multi-phase section. */
+
+/* This rank's lnv community labels (global vertex ids, original local
+ * order) of the last mv_engine_run: the phase assignment. With K the
+ * iteration the run exited at, that is currComm of iteration K-1
+ * (dspl.hpp:1417-1422's pastComm at exit) — the last assignment that
+ * passed the convergence test — or currComm of iteration K when K <= 2,
+ * where pastComm is still the identity. In trace rows (0-based): K-3 for
+ * K >= 3, row 0 for K == 2, the identity for K == 1. Works at any nranks;
+ * costs nothing unless called. Returns non-zero before the first run. */
+int mv_engine_get_communities(mv_engine *e, int64_t *out);
+
+/* Aggregate g (single-rank) by comm[lnv] (labels in [0,nv)) on HIP device
+ * `device`: labels are renumbered dense in ascending order into
+ * map_out[lnv], and every directed fine edge (u, v, w) adds w to the
+ * coarse edge (map[u], map[v]), map[u] == map[v] included (a coarse
+ * self-loop). The result is a CSR with one entry per distinct pair, tails
+ * ascending per row; weights are summed in a fixed order, so two calls
+ * agree bit for bit. Returns NULL with a message on stderr for a label out
+ * of range, a multi-rank graph, or no GPU. No reference counterpart. */
+mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
+                         const int64_t *comm, int64_t *map_out);
+
+/* Multi-phase Louvain (single rank). Level 0 is g; each phase loads the
+ * current level, runs mv_engine_run(lower, thresh), takes the phase
+ * assignment and — unless it merges nothing — aggregates it into a
+ * proposed next level. A proposal whose q is below the current level's is
+ * dropped and ends the run; a kept one ends it when it gains less than
+ * thresh. q of a level = sum_c selfloop_c / W - sum_c deg_c^2 / W^2 on
+ * that level's graph: the modularity of the partition of g the level
+ * represents (the per-phase value mv_engine_run returns is the reference's
+ * hybrid, dspl.hpp:407-456 after :458-471, and is reported separately).
+ * max_phases < 1 means no cap but the safety bound of 64 phases.
+ * The driver loads g itself and LEAVES THE ENGINE HOLDING THE LAST GRAPH
+ * IT LOADED (a device copy of the last level, or of g): call
+ * mv_engine_load_graph again before a plain mv_engine_run. Returns NULL
+ * with a message on stderr, before any communication, when nranks > 1. */
+typedef struct mv_hierarchy mv_hierarchy;
+typedef struct { int iters; double run_mod; int64_t nv_in, ne_in;
+                 double run_ms, coarsen_ms; int kept; } mv_phase_info;
+
+mv_hierarchy *mv_engine_run_multiphase(mv_engine *e, const mv_graph *g,
+                                       double lower, double thresh,
+                                       int max_phases);
+int  mv_hierarchy_phases(const mv_hierarchy *h);   /* phases run, >= 1 */
+int  mv_hierarchy_levels(const mv_hierarchy *h);   /* kept coarse levels L */
+/* Level 1..L (owned by the hierarchy); NULL outside that range. */
+const mv_graph *mv_hierarchy_graph(const mv_hierarchy *h, int level);
+/* Dense map level-1 -> level, for level 1..L; NULL outside. */
+const int64_t *mv_hierarchy_map(const mv_hierarchy *h, int level);
+/* q of level 0..L (level 0: g as singletons); NaN outside. */
+double mv_hierarchy_modularity(const mv_hierarchy *h, int level);
+/* Phase 1..phases: iterations and returned modularity of its run, size of
+ * its input level, wall time of the run and of the aggregation (device
+ * pipeline + the copy to the host level), and whether its proposal was
+ * kept. Non-zero outside the range. */
+int  mv_hierarchy_phase_info(const mv_hierarchy *h, int phase,
+                             mv_phase_info *out);
+/* What phase 1..phases proposed, kept or dropped: its community count and
+ * the q of its coarse graph (nv_in and the current q when it merged
+ * nothing). */
+int  mv_hierarchy_phase_proposal(const mv_hierarchy *h, int phase,
+                                 int64_t *nv_out, double *q_out);
+/* Final community of each vertex of g: the composed kept maps, dense ids
+ * in [0, nv of level L) (the identity when L == 0). */
+const int64_t *mv_hierarchy_communities(const mv_hierarchy *h);
+void mv_hierarchy_free(mv_hierarchy *h);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,6 +8,8 @@ engine without a GPU fails loudly.
 from .api import (  # noqa: F401
     Graph,
     Engine,
+    Hierarchy,
+    coarsen_csr,
     LoopbackSession,
     comm_id,
     lib,

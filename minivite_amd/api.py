@@ -26,6 +26,18 @@ class MvStats(ctypes.Structure):
     ]
 
 
+class MvPhaseInfo(ctypes.Structure):
+    _fields_ = [
+        ("iters", ctypes.c_int),
+        ("run_mod", ctypes.c_double),
+        ("nv_in", ctypes.c_int64),
+        ("ne_in", ctypes.c_int64),
+        ("run_ms", ctypes.c_double),
+        ("coarsen_ms", ctypes.c_double),
+        ("kept", ctypes.c_int),
+    ]
+
+
 def lib():
     global _LIB
     if _LIB is None:
@@ -81,6 +93,30 @@ def lib():
         L.mv_engine_set_trace.argtypes = [vp, pi64, pf64, ctypes.c_int]
         L.mv_engine_get_stats.restype = None
         L.mv_engine_get_stats.argtypes = [vp, ctypes.POINTER(MvStats)]
+        L.mv_engine_get_communities.restype = ctypes.c_int
+        L.mv_engine_get_communities.argtypes = [vp, pi64]
+        L.mv_coarsen_csr.restype = vp
+        L.mv_coarsen_csr.argtypes = [ctypes.c_int, vp, pi64, pi64]
+        L.mv_engine_run_multiphase.restype = vp
+        L.mv_engine_run_multiphase.argtypes = [vp, vp, f64, f64, ctypes.c_int]
+        for name in ("mv_hierarchy_phases", "mv_hierarchy_levels"):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [vp]
+        L.mv_hierarchy_graph.restype = vp
+        L.mv_hierarchy_graph.argtypes = [vp, ctypes.c_int]
+        L.mv_hierarchy_map.restype = pi64
+        L.mv_hierarchy_map.argtypes = [vp, ctypes.c_int]
+        L.mv_hierarchy_modularity.restype = f64
+        L.mv_hierarchy_modularity.argtypes = [vp, ctypes.c_int]
+        L.mv_hierarchy_phase_info.restype = ctypes.c_int
+        L.mv_hierarchy_phase_info.argtypes = [vp, ctypes.c_int,
+                                              ctypes.POINTER(MvPhaseInfo)]
+        L.mv_hierarchy_phase_proposal.restype = ctypes.c_int
+        L.mv_hierarchy_phase_proposal.argtypes = [vp, ctypes.c_int, pi64, pf64]
+        L.mv_hierarchy_communities.restype = pi64
+        L.mv_hierarchy_communities.argtypes = [vp]
+        L.mv_hierarchy_free.restype = None
+        L.mv_hierarchy_free.argtypes = [vp]
         _LIB = L
     return _LIB
 
@@ -150,6 +186,8 @@ class Graph:
     def arrays(self):
         lnv, lne = self.lnv, self.lne
         xadj = np.ctypeslib.as_array(lib().mv_graph_xadj(self.h), (lnv + 1,)).copy()
+        if lne == 0:  # an empty vector's data pointer may be NULL
+            return xadj, np.zeros(0, dtype=np.int64), np.zeros(0)
         tails = np.ctypeslib.as_array(lib().mv_graph_tails(self.h), (lne,)).copy()
         w = np.ctypeslib.as_array(lib().mv_graph_weights(self.h), (lne,)).copy()
         return xadj, tails, w
@@ -161,6 +199,88 @@ class Graph:
     def free(self):
         if getattr(self, "h", None) and self._owns:
             lib().mv_graph_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+
+def coarsen_csr(graph, comm, device=0):
+    """Aggregate the single-rank `graph` by the labels `comm` (values in
+    [0, nv)) on the GPU. Returns (coarse Graph, fine->coarse map)."""
+    comm = np.ascontiguousarray(comm, dtype=np.int64)
+    if comm.shape != (graph.lnv,):
+        raise ValueError("comm must hold one label per vertex")
+    cmap = np.empty(graph.lnv, dtype=np.int64)
+    h = lib().mv_coarsen_csr(device, graph.h, _i64p(comm), _i64p(cmap))
+    if not h:
+        raise RuntimeError("mv_coarsen_csr failed (label out of range, "
+                           "multi-rank graph, or no GPU)")
+    return Graph(h), cmap
+
+
+class Hierarchy:
+    """Result of Engine.run_multiphase: levels 1..levels of coarse graphs,
+    the maps between them, q per level and per-phase records."""
+
+    def __init__(self, handle, nv0):
+        self.h = handle
+        self._nv0 = nv0
+
+    @property
+    def phases(self):
+        return lib().mv_hierarchy_phases(self.h)
+
+    @property
+    def levels(self):
+        return lib().mv_hierarchy_levels(self.h)
+
+    def graph(self, level):
+        """Level 1..levels as a Graph view (owned by the hierarchy)."""
+        g = lib().mv_hierarchy_graph(self.h, level)
+        if not g:
+            raise IndexError(f"level {level} not in 1..{self.levels}")
+        return Graph(g, owns=False)
+
+    def map(self, level):
+        """Dense map from level-1 vertices to level vertices."""
+        p = lib().mv_hierarchy_map(self.h, level)
+        if not p:
+            raise IndexError(f"level {level} not in 1..{self.levels}")
+        n = self._nv0 if level == 1 else self.graph(level - 1).nv
+        return np.ctypeslib.as_array(p, (n,)).copy()
+
+    def modularity(self, level):
+        if not 0 <= level <= self.levels:
+            raise IndexError(f"level {level} not in 0..{self.levels}")
+        return lib().mv_hierarchy_modularity(self.h, level)
+
+    def phase_info(self, phase):
+        """Phase 1..phases: the mv_phase_info fields plus what the phase
+        proposed (nv_out, q_out)."""
+        s = MvPhaseInfo()
+        nv_out, q_out = ctypes.c_int64(0), ctypes.c_double(0.0)
+        if lib().mv_hierarchy_phase_info(self.h, phase, ctypes.byref(s)) != 0:
+            raise IndexError(f"phase {phase} not in 1..{self.phases}")
+        lib().mv_hierarchy_phase_proposal(self.h, phase,
+                                          ctypes.byref(nv_out),
+                                          ctypes.byref(q_out))
+        d = {f: getattr(s, f) for f, _ in s._fields_}
+        d["kept"] = bool(d["kept"])
+        d["nv_out"], d["q_out"] = nv_out.value, q_out.value
+        return d
+
+    @property
+    def communities(self):
+        p = lib().mv_hierarchy_communities(self.h)
+        return np.ctypeslib.as_array(p, (self._nv0,)).copy()
+
+    def free(self):
+        if getattr(self, "h", None):
+            lib().mv_hierarchy_free(self.h)
             self.h = None
 
     def __del__(self):
@@ -238,6 +358,27 @@ class Engine:
         n = min(iters, self._trace_cap)
         return (self._trace_buf.reshape(self._trace_cap, self._lnv)[:n],
                 self._trace_mod[:n])
+
+    def communities(self):
+        """This rank's community labels (global vertex ids) of the last
+        run(): the phase assignment (see mv_engine_get_communities)."""
+        out = np.empty(self._lnv, dtype=np.int64)
+        if lib().mv_engine_get_communities(self.h, _i64p(out)) != 0:
+            raise RuntimeError("mv_engine_get_communities: no run yet")
+        return out
+
+    def run_multiphase(self, graph, lower=-1.0, thresh=1e-6, max_phases=0):
+        """Multi-phase Louvain on `graph` (single rank). The engine is left
+        holding the last level it loaded: load_graph() again before a
+        plain run()."""
+        h = lib().mv_engine_run_multiphase(self.h, graph.h, lower, thresh,
+                                           max_phases)
+        if not h:
+            raise RuntimeError("mv_engine_run_multiphase failed")
+        hier = Hierarchy(h, graph.nv)
+        self._lnv = hier.phase_info(hier.phases)["nv_in"]  # last load
+        self._trace_buf = None  # the loads dropped any armed trace
+        return hier
 
     def stats(self):
         s = MvStats()

@@ -1,0 +1,430 @@
+// coarsen.hip — community aggregation (graph coarsening) on the MI355X: the
+// hot step between two Louvain phases. The reference mini-app stops after
+// phase one and has no counterpart; the definitions are DESIGN.md's
+// multi-phase section.
+//
+// Pipeline (sort-based, insensitive to degree skew):
+//   1. renumber   scatter-mark used labels, exclusive scan, gather
+//                 -> map[v] = dense coarse id in ascending label order
+//   2. keys       one 64-bit key (map[u] << b) | map[tail] per directed
+//                 edge, b = ceil(log2 nc); edge-parallel, the row of an
+//                 edge found per wave (wave-wide row window from xadj,
+//                 then a per-lane search inside the window)
+//   3. sort       hipCUB radix sort over the 2b live key bits; stable, so
+//                 equal keys keep fine-edge order. Unit-weight inputs sort
+//                 keys only
+//   4. runs       run heads -> exclusive scan -> one coarse edge per run;
+//                 row offsets by binary search on the run keys' high half;
+//                 weights summed in a FIXED order: a run of <= 32 edges
+//                 left to right by one thread, a longer run by one block
+//                 (256 strided sequential partials, then a fixed LDS
+//                 tree) — no floating-point atomics anywhere, so results
+//                 are bit-identical run to run. Unit inputs take the run
+//                 length as the weight.
+// Temporary storage is O(lne).
+
+#include <algorithm>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <vector>
+
+#include <hip/hip_runtime.h>
+#include <hipcub/hipcub.hpp>
+
+#include "../../include/minivite_hip.h"
+#include "coarsen.h"
+
+#define HIP_CHECK(x)                                                          \
+    do {                                                                      \
+        hipError_t _e = (x);                                                  \
+        if (_e != hipSuccess) {                                               \
+            std::fprintf(stderr, "HIP error %s at %s:%d: %s\n",               \
+                         hipGetErrorString(_e), __FILE__, __LINE__, #x);      \
+            std::abort();                                                     \
+        }                                                                     \
+    } while (0)
+
+namespace {
+
+using i64 = int64_t;
+using u64 = unsigned long long;
+
+constexpr int kShortRun = 32; // longest run one thread sums on its own
+
+int grid_for(i64 n, int block = 256, int cap = 2048) {
+    i64 g = (n + block - 1) / block;
+    return (int)std::min<i64>(std::max<i64>(g, 1), cap);
+}
+
+// scratch allocation freed at scope exit (never null: floors at 1 element)
+template <class T> struct Scratch {
+    T *ptr = nullptr;
+    explicit Scratch(i64 n) {
+        HIP_CHECK(hipMalloc((void **)&ptr, sizeof(T) * std::max<i64>(n, 1)));
+    }
+    ~Scratch() { (void)hipFree(ptr); }
+    Scratch(const Scratch &) = delete;
+    Scratch &operator=(const Scratch &) = delete;
+    operator T *() const { return ptr; }
+};
+
+// ---- 1. renumber ----
+// used[l] = 1 for every label in use; a label outside [0,nv) raises *err
+// and is not written
+__global__ void k_mark_labels(i64 nv, const i64 *__restrict__ labels,
+                              unsigned *__restrict__ used,
+                              unsigned *__restrict__ err) {
+    for (i64 v = blockIdx.x * (i64)blockDim.x + threadIdx.x; v < nv;
+         v += (i64)gridDim.x * blockDim.x) {
+        const i64 l = labels[v];
+        if (l < 0 || l >= nv) *err = 1u;
+        else used[l] = 1u;
+    }
+}
+
+__global__ void k_gather_map(i64 nv, const i64 *__restrict__ labels,
+                             const unsigned *__restrict__ rank,
+                             i64 *__restrict__ map) {
+    for (i64 v = blockIdx.x * (i64)blockDim.x + threadIdx.x; v < nv;
+         v += (i64)gridDim.x * blockDim.x)
+        map[v] = (i64)rank[labels[v]];
+}
+
+// ---- 2. key generation ----
+// largest r in [lo, hi] with xadj[r] <= e (xadj[lo] <= e is given); empty
+// rows (equal offsets) are skipped because the LAST such r is taken
+__device__ __forceinline__ i64 row_of(const i64 *__restrict__ xadj, i64 lo,
+                                      i64 hi, i64 e) {
+    while (lo < hi) {
+        const i64 mid = (lo + hi + 1) >> 1;
+        if (xadj[mid] <= e) lo = mid;
+        else hi = mid - 1;
+    }
+    return lo;
+}
+
+// One wave owns a tile of 64 consecutive edges: the rows of the tile's
+// first and last edge bound a window (wave-uniform searches over the whole
+// xadj), and each lane then places its own edge inside that window — a hub
+// row costs its waves one window of width 1, never a serial walk.
+__global__ __launch_bounds__(256) void k_coarse_keys(
+    i64 nv, i64 lne, const i64 *__restrict__ xadj,
+    const i64 *__restrict__ tails, const i64 *__restrict__ map, int shift,
+    u64 *__restrict__ keys) {
+    const int lane = threadIdx.x & 63;
+    const i64 wave = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;
+    const i64 nwaves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 e0 = wave * 64; e0 < lne; e0 += nwaves * 64) {
+        const i64 e1 = e0 + 63 < lne ? e0 + 63 : lne - 1;
+        const i64 r0 = row_of(xadj, 0, nv - 1, e0);
+        const i64 r1 = row_of(xadj, r0, nv - 1, e1);
+        const i64 e = e0 + lane;
+        if (e <= e1) {
+            const i64 r = row_of(xadj, r0, r1, e);
+            keys[e] = ((u64)map[r] << shift) | (u64)map[tails[e]];
+        }
+    }
+}
+
+// ---- 4. runs ----
+// head[i] = 1 where a run of equal keys starts; head[lne] = 0 closes the
+// scan so that its last output is the run count
+__global__ void k_run_heads(i64 lne, const u64 *__restrict__ ks,
+                            unsigned *__restrict__ head) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i <= lne;
+         i += (i64)gridDim.x * blockDim.x)
+        head[i] = (i < lne && (i == 0 || ks[i] != ks[i - 1])) ? 1u : 0u;
+}
+
+// run j = pos[i] of head i: its first sorted edge and its key;
+// run_start[nruns] = lne closes the last run
+__global__ void k_run_fill(i64 lne, const u64 *__restrict__ ks,
+                           const unsigned *__restrict__ head,
+                           const unsigned *__restrict__ pos,
+                           i64 *__restrict__ run_start,
+                           u64 *__restrict__ run_key) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i <= lne;
+         i += (i64)gridDim.x * blockDim.x) {
+        if (i == lne) {
+            run_start[pos[lne]] = lne;
+        } else if (head[i]) {
+            run_start[pos[i]] = i;
+            run_key[pos[i]] = ks[i];
+        }
+    }
+}
+
+// coarse row offsets (first run whose high key half is >= c) and tails
+// (the low key half of each run)
+__global__ void k_coarse_rows(i64 nc, i64 nruns, int shift,
+                              const u64 *__restrict__ run_key,
+                              i64 *__restrict__ cxadj,
+                              i64 *__restrict__ ctails) {
+    const u64 mask = (1ull << shift) - 1ull;
+    const i64 n = nruns > nc + 1 ? nruns : nc + 1;
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
+         i += (i64)gridDim.x * blockDim.x) {
+        if (i <= nc) {
+            const u64 key = (u64)i << shift;
+            i64 lo = 0, hi = nruns;
+            while (lo < hi) {
+                const i64 mid = (lo + hi) >> 1;
+                if (run_key[mid] < key) lo = mid + 1;
+                else hi = mid;
+            }
+            cxadj[i] = lo;
+        }
+        if (i < nruns) ctails[i] = (i64)(run_key[i] & mask);
+    }
+}
+
+// unit inputs: the weight of a coarse edge is the number of fine edges
+__global__ void k_run_lengths(i64 nruns, const i64 *__restrict__ run_start,
+                              double *__restrict__ cw) {
+    for (i64 j = blockIdx.x * (i64)blockDim.x + threadIdx.x; j < nruns;
+         j += (i64)gridDim.x * blockDim.x)
+        cw[j] = (double)(run_start[j + 1] - run_start[j]);
+}
+
+// short runs: one thread, left to right; longer runs are queued (the queue
+// order is arbitrary, each queued run's sum is not)
+__global__ void k_reduce_short(i64 nruns, const i64 *__restrict__ run_start,
+                               const double *__restrict__ ws,
+                               double *__restrict__ cw,
+                               i64 *__restrict__ long_list,
+                               u64 *__restrict__ long_count) {
+    for (i64 j = blockIdx.x * (i64)blockDim.x + threadIdx.x; j < nruns;
+         j += (i64)gridDim.x * blockDim.x) {
+        const i64 s = run_start[j], t = run_start[j + 1];
+        if (t - s > kShortRun) {
+            long_list[atomicAdd(long_count, 1ull)] = j;
+            continue;
+        }
+        double a = 0.0;
+        for (i64 i = s; i < t; i++) a += ws[i];
+        cw[j] = a;
+    }
+}
+
+// long runs: one block per run at a time, any length — thread t sums
+// elements s+t, s+t+256, ... in order, then a fixed 256-leaf LDS tree
+__global__ __launch_bounds__(256) void k_reduce_long(
+    const i64 *__restrict__ long_list, const u64 *__restrict__ long_count,
+    const i64 *__restrict__ run_start, const double *__restrict__ ws,
+    double *__restrict__ cw) {
+    __shared__ double sb[256];
+    const i64 n = (i64)*long_count;
+    for (i64 k = blockIdx.x; k < n; k += gridDim.x) {
+        const i64 j = long_list[k];
+        const i64 s = run_start[j], t = run_start[j + 1];
+        double a = 0.0;
+        for (i64 i = s + threadIdx.x; i < t; i += 256) a += ws[i];
+        sb[threadIdx.x] = a;
+        __syncthreads();
+        for (int off = 128; off > 0; off >>= 1) {
+            if ((int)threadIdx.x < off)
+                sb[threadIdx.x] += sb[threadIdx.x + off];
+            __syncthreads();
+        }
+        if (threadIdx.x == 0) cw[j] = sb[0];
+        __syncthreads();
+    }
+}
+
+// exclusive prefix sum of n unsigned values (n < 2^31)
+void exclusive_sum(hipStream_t st, const unsigned *in, unsigned *out, i64 n) {
+    size_t bytes = 0;
+    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n,
+                                           st);
+    Scratch<char> tmp((i64)bytes);
+    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, in, out,
+                                               (int)n, st));
+    HIP_CHECK(hipStreamSynchronize(st)); // tmp dies with this scope
+}
+
+} // namespace
+
+void mv_coarse_dev_free(mv_coarse_dev *c) {
+    if (c->d_map) (void)hipFree(c->d_map);
+    if (c->d_xadj) (void)hipFree(c->d_xadj);
+    if (c->d_tails) (void)hipFree(c->d_tails);
+    if (c->d_w) (void)hipFree(c->d_w);
+    *c = mv_coarse_dev{};
+}
+
+int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
+                      const int64_t *d_xadj, const int64_t *d_tails,
+                      const double *d_w, const int64_t *d_labels,
+                      bool stop_if_identity, mv_coarse_dev *out) {
+    *out = mv_coarse_dev{};
+    if (nv < 1 || nv >= (1ll << 31) || lne < 0 || lne >= (1ll << 31) - 1) {
+        std::fprintf(stderr,
+                     "mv_coarsen: need 1 <= nv < 2^31 and lne < 2^31 - 1 "
+                     "(nv=%lld lne=%lld)\n",
+                     (long long)nv, (long long)lne);
+        return -1;
+    }
+
+    // ---- 1. renumber ----
+    Scratch<unsigned> used(nv + 2), rank(nv + 1);
+    unsigned *err = used + nv + 1; // one word past the scan's closing 0
+    HIP_CHECK(hipMemsetAsync(used, 0, 4 * (nv + 2), st));
+    k_mark_labels<<<grid_for(nv), 256, 0, st>>>(nv, d_labels, used, err);
+    exclusive_sum(st, used, rank, nv + 1);
+    unsigned h_nc = 0, h_err = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_nc, rank + nv, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    if (h_err) {
+        std::fprintf(stderr,
+                     "mv_coarsen: community label outside [0, nv=%lld)\n",
+                     (long long)nv);
+        return -1;
+    }
+    const i64 nc = h_nc;
+    out->nc = nc;
+    HIP_CHECK(hipMalloc((void **)&out->d_map, 8 * nv));
+    k_gather_map<<<grid_for(nv), 256, 0, st>>>(nv, d_labels, rank,
+                                               out->d_map);
+    if (stop_if_identity && nc == nv) {
+        HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+
+    // ---- 2./3. keys + sort over the 2*shift live bits ----
+    int shift = 1;
+    while ((1ll << shift) < nc) shift++;
+    HIP_CHECK(hipMalloc((void **)&out->d_xadj, 8 * (nc + 1)));
+    if (lne == 0) {
+        HIP_CHECK(hipMemsetAsync(out->d_xadj, 0, 8 * (nc + 1), st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        return 0;
+    }
+    Scratch<u64> keys(lne), ks(lne);
+    Scratch<double> ws(d_w ? lne : 0);
+    k_coarse_keys<<<grid_for(lne), 256, 0, st>>>(nv, lne, d_xadj, d_tails,
+                                                 out->d_map, shift, keys);
+    {
+        size_t bytes = 0;
+        if (d_w)
+            (void)hipcub::DeviceRadixSort::SortPairs(
+                nullptr, bytes, keys.ptr, ks.ptr, d_w, ws.ptr, (int)lne, 0,
+                2 * shift, st);
+        else
+            (void)hipcub::DeviceRadixSort::SortKeys(
+                nullptr, bytes, keys.ptr, ks.ptr, (int)lne, 0, 2 * shift, st);
+        Scratch<char> tmp((i64)bytes);
+        if (d_w)
+            HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
+                tmp.ptr, bytes, keys.ptr, ks.ptr, d_w, ws.ptr, (int)lne, 0,
+                2 * shift, st));
+        else
+            HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(
+                tmp.ptr, bytes, keys.ptr, ks.ptr, (int)lne, 0, 2 * shift,
+                st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    // ---- 4. runs ----
+    Scratch<unsigned> head(lne + 1), pos(lne + 1);
+    k_run_heads<<<grid_for(lne + 1), 256, 0, st>>>(lne, ks, head);
+    exclusive_sum(st, head, pos, lne + 1);
+    unsigned h_runs = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_runs, pos + lne, 4, hipMemcpyDeviceToHost,
+                             st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const i64 nruns = h_runs;
+    out->ne = nruns;
+    HIP_CHECK(hipMalloc((void **)&out->d_tails, 8 * nruns));
+    HIP_CHECK(hipMalloc((void **)&out->d_w, 8 * nruns));
+    Scratch<i64> run_start(nruns + 1);
+    Scratch<u64> run_key(nruns);
+    k_run_fill<<<grid_for(lne + 1), 256, 0, st>>>(lne, ks, head, pos,
+                                                  run_start, run_key);
+    k_coarse_rows<<<grid_for(std::max(nruns, nc + 1)), 256, 0, st>>>(
+        nc, nruns, shift, run_key, out->d_xadj, out->d_tails);
+    if (!d_w) {
+        k_run_lengths<<<grid_for(nruns), 256, 0, st>>>(nruns, run_start,
+                                                       out->d_w);
+        HIP_CHECK(hipStreamSynchronize(st));
+    } else {
+        Scratch<i64> long_list(nruns);
+        Scratch<u64> long_count(1);
+        HIP_CHECK(hipMemsetAsync(long_count, 0, 8, st));
+        k_reduce_short<<<grid_for(nruns), 256, 0, st>>>(
+            nruns, run_start, ws, out->d_w, long_list, long_count);
+        k_reduce_long<<<grid_for(nruns, 1, 1024), 256, 0, st>>>(
+            long_list, long_count, run_start, ws, out->d_w);
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    return 0;
+}
+
+extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
+                                    const int64_t *comm, int64_t *map_out) {
+    const i64 nv = mv_graph_nv(g), lne = mv_graph_lne(g);
+    if (mv_graph_lnv(g) != nv) {
+        std::fprintf(stderr, "mv_coarsen_csr: single-rank graphs only "
+                             "(lnv != nv)\n");
+        return nullptr;
+    }
+    const i64 *xadj = mv_graph_xadj(g), *tails = mv_graph_tails(g);
+    const double *w = mv_graph_weights(g);
+    for (i64 k = 0; k < lne; k++)
+        if (tails[k] < 0 || tails[k] >= nv) {
+            std::fprintf(stderr, "mv_coarsen_csr: tail out of range\n");
+            return nullptr;
+        }
+    if (xadj[0] != 0 || xadj[nv] != lne) {
+        std::fprintf(stderr, "mv_coarsen_csr: malformed xadj\n");
+        return nullptr;
+    }
+    for (i64 v = 0; v < nv; v++)
+        if (xadj[v] > xadj[v + 1]) {
+            std::fprintf(stderr, "mv_coarsen_csr: malformed xadj\n");
+            return nullptr;
+        }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= device) {
+        std::fprintf(stderr,
+                     "mv_coarsen_csr: no HIP device %d (found %d). There is "
+                     "no CPU fallback.\n",
+                     device, ndev);
+        return nullptr;
+    }
+    HIP_CHECK(hipSetDevice(device));
+    bool unit = true;
+    for (i64 k = 0; k < lne && unit; k++) unit = w[k] == 1.0;
+
+    hipStream_t st = nullptr; // the default stream: a one-shot entry
+    Scratch<i64> d_xadj(nv + 1), d_tails(lne), d_comm(nv);
+    Scratch<double> d_w(unit ? 0 : lne);
+    HIP_CHECK(hipMemcpy(d_xadj, xadj, 8 * (nv + 1), hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_tails, tails, 8 * lne, hipMemcpyHostToDevice));
+    HIP_CHECK(hipMemcpy(d_comm, comm, 8 * nv, hipMemcpyHostToDevice));
+    if (!unit) HIP_CHECK(hipMemcpy(d_w, w, 8 * lne, hipMemcpyHostToDevice));
+
+    mv_coarse_dev c;
+    if (mv_coarsen_device(st, nv, lne, d_xadj, d_tails,
+                          unit ? nullptr : d_w.ptr, d_comm, false, &c) != 0) {
+        mv_coarse_dev_free(&c);
+        return nullptr;
+    }
+    std::vector<i64> cx(c.nc + 1), ct(c.ne);
+    std::vector<double> cw(c.ne);
+    HIP_CHECK(hipMemcpy(map_out, c.d_map, 8 * nv, hipMemcpyDeviceToHost));
+    HIP_CHECK(hipMemcpy(cx.data(), c.d_xadj, 8 * (c.nc + 1),
+                        hipMemcpyDeviceToHost));
+    if (c.ne) {
+        HIP_CHECK(hipMemcpy(ct.data(), c.d_tails, 8 * c.ne,
+                            hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cw.data(), c.d_w, 8 * c.ne,
+                            hipMemcpyDeviceToHost));
+    }
+    const i64 parts[2] = {0, c.nc};
+    mv_graph *cg = mv_graph_from_csr(c.nc, 0, 1, parts, c.nc, c.ne, cx.data(),
+                                     ct.data(), cw.data());
+    mv_coarse_dev_free(&c);
+    return cg;
+}

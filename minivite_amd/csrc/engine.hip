@@ -44,6 +44,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <cstdint>
 #include <cstdio>
@@ -58,6 +59,7 @@
 #include <rccl/rccl.h>
 
 #include "../../include/minivite_hip.h"
+#include "coarsen.h"
 
 #define HIP_CHECK(x)                                                          \
     do {                                                                      \
@@ -1383,6 +1385,12 @@ struct mv_graph_state {
     i64 hash_hub_elems = 0; // prefix the wave kernel atomics into (needs
                             // zeroed accumulators each iteration)
 
+    // phase assignment of the last run (mv_engine_get_communities): the
+    // rotated buffer that holds it — past at exit, or curr when past is
+    // still the identity (K <= 2) — converted to labels only on request
+    const i64 *res_src = nullptr;
+    DevBuf<i64> d_res; // lnv labels, original local order
+
     // trace
     i64 *trace_target = nullptr;
     double *trace_mod = nullptr;
@@ -2676,6 +2684,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         if (dbg)
             std::fprintf(stderr, "[sweep] iter %zu: %.3f ms\n", k / 2 + 1, ms);
     }
+    e->res_src = numIters <= 2 ? d_curr : d_past;
     e->stats.iters = numIters;
     e->stats.total_ms = std::chrono::duration<double, std::milli>(
                             std::chrono::steady_clock::now() - t_start)
@@ -2683,5 +2692,232 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     *iters_out = numIters;
     return prevMod; // dspl.hpp:1440
 }
+
+} // extern "C"
+
+// ------------------------------------------------------------------------
+// Phase assignment + multi-phase driver (multi-phase section).
+// The reference mini-app stops after phase one; nothing below has a
+// counterpart there.
+
+// The last run's phase assignment as LABELS in original local order, in
+// e->d_res (device). Null before the first run.
+static const i64 *phase_labels_device(mv_engine *e) {
+    if (!e->res_src) return nullptr;
+    const i64 lnv = e->lnv;
+    e->d_res.reserve(lnv);
+    if (e->nranks == 1)
+        k_depermute32<<<grid_for(lnv), 256, 0, e->stream>>>(
+            lnv, e->d_sigma, e->d_sigma_inv, (const unsigned *)e->res_src,
+            e->d_res);
+    else
+        k_depermute<<<grid_for(lnv), 256, 0, e->stream>>>(
+            lnv, e->d_sigma_inv, e->res_src, e->d_res);
+    return e->d_res;
+}
+
+// q of a level's graph: sum_c selfloop_c / W - sum_c deg_c^2 / W^2, in
+// row order on the host (levels are host-resident anyway)
+static double level_modularity(const mv_graph *g) {
+    const i64 nv = mv_graph_lnv(g);
+    const i64 *xadj = mv_graph_xadj(g), *tails = mv_graph_tails(g);
+    const double *w = mv_graph_weights(g);
+    double W = 0.0, loops = 0.0, deg2 = 0.0;
+    for (i64 v = 0; v < nv; v++) {
+        double d = 0.0;
+        for (i64 k = xadj[v]; k < xadj[v + 1]; k++) {
+            d += w[k];
+            if (tails[k] == v) loops += w[k];
+        }
+        W += d;
+        deg2 += d * d;
+    }
+    return W == 0.0 ? 0.0 : loops / W - deg2 / (W * W);
+}
+
+struct mv_hierarchy {
+    std::vector<mv_graph *> graphs;     // [0] unused (the caller's graph)
+    std::vector<std::vector<i64>> maps; // [0] unused
+    std::vector<double> q;              // levels 0..L
+    std::vector<mv_phase_info> info;    // phases 1..P at [0..P)
+    std::vector<i64> prop_nv;           // what each phase proposed
+    std::vector<double> prop_q;
+    std::vector<i64> comm;              // nv0 dense ids
+    ~mv_hierarchy() {
+        for (auto *g : graphs)
+            if (g) mv_graph_free(g);
+    }
+};
+
+static const int kMaxPhases = 64; // every kept level has fewer vertices
+                                  // than the one before; RGG 2^22 needs 9
+
+extern "C" {
+
+int mv_engine_get_communities(mv_engine *e, int64_t *out) {
+    HIP_CHECK(hipSetDevice(e->device));
+    const i64 *lab = phase_labels_device(e);
+    if (!lab) {
+        std::fprintf(stderr, "mv_engine_get_communities: no run yet\n");
+        return -1;
+    }
+    HIP_CHECK(hipMemcpyAsync(out, lab, 8 * e->lnv, hipMemcpyDeviceToHost,
+                             e->stream));
+    HIP_CHECK(hipStreamSynchronize(e->stream));
+    return 0;
+}
+
+mv_hierarchy *mv_engine_run_multiphase(mv_engine *e, const mv_graph *g,
+                                       double lower, double thresh,
+                                       int max_phases) {
+    if (e->nranks > 1) {
+        std::fprintf(stderr,
+                     "mv_engine_run_multiphase: single-rank only (nranks=%d);"
+                     " multi-rank coarsening needs an edge redistribution\n",
+                     e->nranks);
+        return nullptr;
+    }
+    if (mv_graph_lnv(g) != mv_graph_nv(g)) {
+        std::fprintf(stderr,
+                     "mv_engine_run_multiphase: graph is a multi-rank slice\n");
+        return nullptr;
+    }
+    HIP_CHECK(hipSetDevice(e->device));
+    const int cap = max_phases >= 1 ? max_phases : kMaxPhases;
+    auto *h = new mv_hierarchy;
+    h->graphs.push_back(nullptr);
+    h->maps.emplace_back();
+    h->q.push_back(level_modularity(g));
+    const mv_graph *cur = g;
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) {
+        return std::chrono::duration<double, std::milli>(clk::now() - t0)
+            .count();
+    };
+    for (int phase = 1; phase <= cap; phase++) {
+        if (mv_engine_load_graph(e, cur) != 0) {
+            delete h;
+            return nullptr;
+        }
+        mv_phase_info pi{};
+        pi.nv_in = e->lnv;
+        pi.ne_in = e->lne;
+        auto t0 = clk::now();
+        pi.run_mod = mv_engine_run(e, lower, thresh, &pi.iters);
+        pi.run_ms = ms_since(t0);
+        h->info.push_back(pi);
+        h->prop_nv.push_back(pi.nv_in);
+        h->prop_q.push_back(h->q.back());
+        mv_phase_info &info = h->info.back();
+
+        // aggregate straight off the CSR the engine holds on the device
+        t0 = clk::now();
+        mv_coarse_dev c;
+        if (mv_coarsen_device(e->stream, e->lnv, e->lne, e->d_xadj,
+                              e->d_tails,
+                              e->unit_weights ? nullptr : e->d_ew.get(),
+                              phase_labels_device(e),
+                              /*stop_if_identity*/ true, &c) != 0) {
+            mv_coarse_dev_free(&c);
+            delete h;
+            return nullptr;
+        }
+        if (c.nc == e->lnv) { // no merge: the hierarchy is complete
+            mv_coarse_dev_free(&c);
+            break;
+        }
+        const double dev_ms = ms_since(t0); // the kernels, synchronised
+        std::vector<i64> map(e->lnv), cx(c.nc + 1), ct(c.ne);
+        std::vector<double> cw(c.ne);
+        HIP_CHECK(hipMemcpy(map.data(), c.d_map, 8 * e->lnv,
+                            hipMemcpyDeviceToHost));
+        HIP_CHECK(hipMemcpy(cx.data(), c.d_xadj, 8 * (c.nc + 1),
+                            hipMemcpyDeviceToHost));
+        if (c.ne) {
+            HIP_CHECK(hipMemcpy(ct.data(), c.d_tails, 8 * c.ne,
+                                hipMemcpyDeviceToHost));
+            HIP_CHECK(hipMemcpy(cw.data(), c.d_w, 8 * c.ne,
+                                hipMemcpyDeviceToHost));
+        }
+        const double copy_ms = ms_since(t0) - dev_ms;
+        const i64 parts[2] = {0, c.nc};
+        mv_graph *ng = mv_graph_from_csr(c.nc, 0, 1, parts, c.nc, c.ne,
+                                         cx.data(), ct.data(), cw.data());
+        mv_coarse_dev_free(&c);
+        info.coarsen_ms = ms_since(t0);
+        if (getenv("MV_COARSEN_DEBUG"))
+            std::fprintf(stderr,
+                         "[coarsen] phase %d: device %.3f ms, D2H %.3f ms, "
+                         "host level build %.3f ms\n",
+                         phase, dev_ms, copy_ms,
+                         info.coarsen_ms - dev_ms - copy_ms);
+        if (!ng) {
+            delete h;
+            return nullptr;
+        }
+        const double qn = level_modularity(ng);
+        h->prop_nv.back() = mv_graph_nv(ng);
+        h->prop_q.back() = qn;
+        if (qn < h->q.back()) { // the proposal lowers q: drop it
+            mv_graph_free(ng);
+            break;
+        }
+        info.kept = 1;
+        const double gain = qn - h->q.back();
+        h->graphs.push_back(ng);
+        h->maps.push_back(std::move(map));
+        h->q.push_back(qn);
+        cur = ng;
+        if (gain < thresh) break;
+    }
+    h->comm.resize(mv_graph_nv(g));
+    for (size_t v = 0; v < h->comm.size(); v++) {
+        i64 c = (i64)v;
+        for (size_t k = 1; k < h->maps.size(); k++) c = h->maps[k][c];
+        h->comm[v] = c;
+    }
+    return h;
+}
+
+int mv_hierarchy_phases(const mv_hierarchy *h) { return (int)h->info.size(); }
+
+int mv_hierarchy_levels(const mv_hierarchy *h) {
+    return (int)h->graphs.size() - 1;
+}
+
+const mv_graph *mv_hierarchy_graph(const mv_hierarchy *h, int level) {
+    return level >= 1 && level < (int)h->graphs.size() ? h->graphs[level]
+                                                       : nullptr;
+}
+
+const int64_t *mv_hierarchy_map(const mv_hierarchy *h, int level) {
+    return level >= 1 && level < (int)h->maps.size() ? h->maps[level].data()
+                                                     : nullptr;
+}
+
+double mv_hierarchy_modularity(const mv_hierarchy *h, int level) {
+    return level >= 0 && level < (int)h->q.size() ? h->q[level] : NAN;
+}
+
+int mv_hierarchy_phase_info(const mv_hierarchy *h, int phase,
+                            mv_phase_info *out) {
+    if (phase < 1 || phase > (int)h->info.size()) return -1;
+    *out = h->info[phase - 1];
+    return 0;
+}
+
+int mv_hierarchy_phase_proposal(const mv_hierarchy *h, int phase,
+                                int64_t *nv_out, double *q_out) {
+    if (phase < 1 || phase > (int)h->info.size()) return -1;
+    *nv_out = h->prop_nv[phase - 1];
+    *q_out = h->prop_q[phase - 1];
+    return 0;
+}
+
+const int64_t *mv_hierarchy_communities(const mv_hierarchy *h) {
+    return h->comm.data();
+}
+
+void mv_hierarchy_free(mv_hierarchy *h) { delete h; }
 
 } // extern "C"

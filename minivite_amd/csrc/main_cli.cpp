@@ -13,6 +13,10 @@
 //    the LCG path.
 //  * -p takes the reference semantics but a fixed seed (graph.hpp:990's
 //    time(0)^getpid() is unreproducible); set MV_RAND_SEED to vary it.
+//  * -m (no reference counterpart) runs the multi-phase driver on one GPU
+//    and appends one line per phase plus a final line to the result block;
+//    -o FILE writes one community per vertex: the final dense ids with -m,
+//    the phase-assignment labels without.
 
 #include <atomic>
 #include <chrono>
@@ -35,8 +39,10 @@ int main(int argc, char *argv[]) {
     double threshold = 1.0E-6, randomEdgePercent = 0.0;
     long nvRGG = 0;
     int ngpus = 1;
+    bool multiPhase = false;
+    std::string commFileName;
     int ret;
-    while ((ret = getopt(argc, argv, "f:br:t:n:wlp:sg:")) != -1) {
+    while ((ret = getopt(argc, argv, "f:br:t:n:wlp:sg:mo:")) != -1) {
         switch (ret) {
         case 'f': inputFileName = optarg; break;
         case 'b': readBalanced = true; break;
@@ -51,6 +57,8 @@ int main(int argc, char *argv[]) {
         case 'p': randomEdgePercent = atof(optarg); break;
         case 's': showGraph = true; break;
         case 'g': ngpus = atoi(optarg); break;
+        case 'm': multiPhase = true; break;
+        case 'o': commFileName = optarg; break;
         default:
             std::fprintf(stderr, "Option not recognized\n");
             return 1;
@@ -59,7 +67,12 @@ int main(int argc, char *argv[]) {
     if (argc == 1 || (!generateGraph && inputFileName.empty())) {
         std::fprintf(stderr,
                      "usage: mv355 [-n nv -l | -f file.bin [-b]] [-t thresh] "
-                     "[-w] [-p pct] [-g ngpus]\n");
+                     "[-w] [-p pct] [-g ngpus] [-m] [-o communities.txt]\n");
+        return 1;
+    }
+    if (multiPhase && ngpus > 1) {
+        std::fprintf(stderr, "mv355: -m is single-GPU only (got -g %d)\n",
+                     ngpus);
         return 1;
     }
     if (generateGraph && !randomNumberLCG)
@@ -150,6 +163,8 @@ int main(int argc, char *argv[]) {
     if (ngpus > 1 && mv_comm_id(cid) != 0) return 1;
     std::vector<double> mods(ngpus), times(ngpus);
     std::vector<int> iters(ngpus);
+    std::vector<std::vector<int64_t>> comms(ngpus);
+    mv_hierarchy *hier = nullptr;
     std::atomic<int> failed{0};
     {
         std::vector<std::thread> th;
@@ -163,11 +178,29 @@ int main(int argc, char *argv[]) {
                 }
                 auto t0 = std::chrono::steady_clock::now();
                 int it = 0;
-                mods[r] = mv_engine_run(e, -1.0, threshold, &it);
+                if (multiPhase) {
+                    hier = mv_engine_run_multiphase(e, graphs[r], -1.0,
+                                                    threshold, 0);
+                    if (!hier) {
+                        failed = 1;
+                        return;
+                    }
+                    mv_phase_info p1;
+                    mv_hierarchy_phase_info(hier, 1, &p1);
+                    mods[r] = p1.run_mod; // the block reports phase one
+                    it = p1.iters;
+                } else {
+                    mods[r] = mv_engine_run(e, -1.0, threshold, &it);
+                }
                 times[r] = std::chrono::duration<double>(
                                std::chrono::steady_clock::now() - t0)
                                .count();
                 iters[r] = it;
+                if (!commFileName.empty() && !multiPhase) {
+                    comms[r].resize(mv_graph_lnv(graphs[r]));
+                    if (mv_engine_get_communities(e, comms[r].data()) != 0)
+                        failed = 1;
+                }
                 mv_engine_destroy(e);
             });
         for (auto &t : th) t.join();
@@ -194,6 +227,52 @@ int main(int argc, char *argv[]) {
                 mods[0] * avgt);
     std::printf("-------------------------------------------------------\n");
 
+    if (hier) {
+        // no reference counterpart: one line per phase, then the result
+        const int phases = mv_hierarchy_phases(hier);
+        for (int p = 1; p <= phases; p++) {
+            mv_phase_info pi;
+            int64_t nv_out = 0;
+            double q = 0;
+            mv_hierarchy_phase_info(hier, p, &pi);
+            mv_hierarchy_phase_proposal(hier, p, &nv_out, &q);
+            if (nv_out == pi.nv_in)
+                std::printf("Phase %d: vertices in %lld, iterations %d, "
+                            "modularity %g, no merges\n",
+                            p, (long long)pi.nv_in, pi.iters, pi.run_mod);
+            else
+                std::printf("Phase %d: vertices in %lld, iterations %d, "
+                            "modularity %g, vertices out %lld, q %.10g%s\n",
+                            p, (long long)pi.nv_in, pi.iters, pi.run_mod,
+                            (long long)nv_out, q,
+                            pi.kept ? "" : " (dropped)");
+        }
+        const int L = mv_hierarchy_levels(hier);
+        const int64_t ncomm = L ? mv_graph_nv(mv_hierarchy_graph(hier, L))
+                                : mv_graph_nv(graphs[0]);
+        std::printf("Communities, q: %lld, %.10g\n", (long long)ncomm,
+                    mv_hierarchy_modularity(hier, L));
+        std::printf("-------------------------------------------------------\n");
+    }
+    if (!commFileName.empty()) {
+        FILE *f = std::fopen(commFileName.c_str(), "w");
+        if (!f) {
+            std::perror(commFileName.c_str());
+            return 1;
+        }
+        if (hier) {
+            const int64_t *c = mv_hierarchy_communities(hier);
+            const int64_t n = mv_graph_nv(graphs[0]);
+            for (int64_t v = 0; v < n; v++)
+                std::fprintf(f, "%lld\n", (long long)c[v]);
+        } else {
+            for (int r = 0; r < ngpus; r++)
+                for (int64_t c : comms[r])
+                    std::fprintf(f, "%lld\n", (long long)c);
+        }
+        std::fclose(f);
+    }
+    if (hier) mv_hierarchy_free(hier);
     for (auto *g : graphs) mv_graph_free(g);
     return 0;
 }
