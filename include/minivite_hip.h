@@ -137,6 +137,37 @@ typedef struct {
 } mv_stats;
 void mv_engine_get_stats(const mv_engine *e, mv_stats *out);
 
+/* Which K4 kernel shapes the last mv_engine_run launched, and the routing
+ * state that chose them (tests assert on it; nothing here is timed).
+ * The counters are host-side launch counts, zeroed where mv_stats is
+ * (graph load and the start of a run); a launch over an empty range is not
+ * issued and not counted. With the halo overlap on, the general and
+ * iteration-1 kernels are launched twice per iteration (exports, then the
+ * interior). The state fields are read from the engine when the call is
+ * made: at nranks > 1 they describe the last run's setup (ghost discovery
+ * and the SELL build happen inside the run), `overlap` after the
+ * collective decision. */
+typedef struct {
+    int64_t general;          /* k4_sweep launches, all SLOTS together */
+    int64_t general_slots[7]; /* ... by SLOTS = 4, 8, 12, 16, 24, 32, 48 */
+    int64_t iter1_label_order;    /* k4_sweep_iter1, LBL_ASC = true */
+    int64_t iter1_internal_order; /* k4_sweep_iter1, LBL_ASC = false */
+    int64_t hi;               /* k4_sweep_hi launches */
+    int64_t lh;               /* k4_sweep_lh launches */
+    int64_t nhi, nlh;         /* degree-sorted positions [0,nhi) take the
+                               * wave-per-vertex kernel, [nhi,nlh) the
+                               * lane-hash kernel, [nlh,lnv) the others */
+    int64_t nghost;           /* distinct remote tails of this rank */
+    int64_t ssz;              /* export entries, summed over the peers */
+    int64_t nexp;             /* exported vertices placed first (overlap) */
+    int skewed;               /* max local degree > 256 */
+    int overlap;              /* halo #1a overlapped in the last run */
+    int rows_sorted;          /* input rows had ascending tails */
+    int sell_sorted;          /* SELL rows re-sorted by internal index */
+    int unit_weights;         /* every local edge weight == 1.0 */
+} mv_sweep_info;
+void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
+
 /* ---- beyond phase one: assignment, aggregation, multi-phase driver ----
  * The reference mini-app stops after one phase and never hands the
  * assignment out (main.cpp:164-196 prints modularity and iterations only);

@@ -26,6 +26,30 @@ class MvStats(ctypes.Structure):
     ]
 
 
+SWEEP_SLOTS = (4, 8, 12, 16, 24, 32, 48)  # general_slots index -> SLOTS
+
+
+class MvSweepInfo(ctypes.Structure):
+    _fields_ = [
+        ("general", ctypes.c_int64),
+        ("general_slots", ctypes.c_int64 * len(SWEEP_SLOTS)),
+        ("iter1_label_order", ctypes.c_int64),
+        ("iter1_internal_order", ctypes.c_int64),
+        ("hi", ctypes.c_int64),
+        ("lh", ctypes.c_int64),
+        ("nhi", ctypes.c_int64),
+        ("nlh", ctypes.c_int64),
+        ("nghost", ctypes.c_int64),
+        ("ssz", ctypes.c_int64),
+        ("nexp", ctypes.c_int64),
+        ("skewed", ctypes.c_int),
+        ("overlap", ctypes.c_int),
+        ("rows_sorted", ctypes.c_int),
+        ("sell_sorted", ctypes.c_int),
+        ("unit_weights", ctypes.c_int),
+    ]
+
+
 class MvPhaseInfo(ctypes.Structure):
     _fields_ = [
         ("iters", ctypes.c_int),
@@ -93,6 +117,9 @@ def lib():
         L.mv_engine_set_trace.argtypes = [vp, pi64, pf64, ctypes.c_int]
         L.mv_engine_get_stats.restype = None
         L.mv_engine_get_stats.argtypes = [vp, ctypes.POINTER(MvStats)]
+        L.mv_engine_get_sweep_info.restype = None
+        L.mv_engine_get_sweep_info.argtypes = [vp,
+                                               ctypes.POINTER(MvSweepInfo)]
         L.mv_engine_get_communities.restype = ctypes.c_int
         L.mv_engine_get_communities.argtypes = [vp, pi64]
         L.mv_coarsen_csr.restype = vp
@@ -384,6 +411,15 @@ class Engine:
         s = MvStats()
         lib().mv_engine_get_stats(self.h, ctypes.byref(s))
         return {f: getattr(s, f) for f, _ in s._fields_}
+
+    def sweep_info(self):
+        """Kernel shapes launched by the last run() and the routing state
+        behind them (mv_sweep_info); general_slots becomes {SLOTS: count}."""
+        s = MvSweepInfo()
+        lib().mv_engine_get_sweep_info(self.h, ctypes.byref(s))
+        d = {f: getattr(s, f) for f, _ in s._fields_}
+        d["general_slots"] = dict(zip(SWEEP_SLOTS, s.general_slots))
+        return d
 
     def destroy(self):
         if getattr(self, "h", None):

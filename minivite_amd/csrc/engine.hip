@@ -1189,6 +1189,12 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1(
     }
 }
 
+// index of a k4_sweep SLOTS value in mv_sweep_info::general_slots
+constexpr int mv_sweep_slot_index(int slots) {
+    return slots == 4 ? 0 : slots == 8 ? 1 : slots == 12 ? 2 : slots == 16 ? 3
+         : slots == 24 ? 4 : slots == 32 ? 5 : 6;
+}
+
 int grid_for(i64 n, int block = 256, int cap = 2048) {
     i64 g = (n + block - 1) / block;
     return (int)std::min<i64>(std::max<i64>(g, 1), cap);
@@ -1411,6 +1417,7 @@ struct mv_engine : mv_graph_state {
     hipEvent_t ev_halo = nullptr;  // next-iteration pipeline done [stream2]
 
     mv_stats stats{};
+    mv_sweep_info sweep{}; // launch counters only; state is read on request
     std::vector<hipEvent_t> ev_pool;
     int ev_used = 0;
 
@@ -1623,6 +1630,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     if (e->nranks == 1) build_sell(e);
     HIP_CHECK(hipDeviceSynchronize());
     e->stats = mv_stats{};
+    e->sweep = mv_sweep_info{};
     e->stats.edges_local = lne;
     return 0;
 }
@@ -1636,6 +1644,20 @@ void mv_engine_set_trace(mv_engine *e, int64_t *target_trace, double *mod_trace,
 }
 
 void mv_engine_get_stats(const mv_engine *e, mv_stats *out) { *out = e->stats; }
+
+void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out) {
+    *out = e->sweep; // the launch counters of the last run
+    out->nhi = e->nhi;
+    out->nlh = e->nlh;
+    out->nghost = e->nghost;
+    out->ssz = e->ssz;
+    out->nexp = e->nexp;
+    out->skewed = e->skewed;
+    out->overlap = e->overlap;
+    out->rows_sorted = e->rows_sorted;
+    out->sell_sorted = e->sell_sorted;
+    out->unit_weights = e->unit_weights;
+}
 
 // ------------------------------------------------------------------------
 // Transport seam. Three primitives — exchange(), allgather_counts() and
@@ -2300,6 +2322,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     const int p = e->nranks;
     e->ev_used = 0;
     e->stats = mv_stats{};
+    e->sweep = mv_sweep_info{};
     e->stats.edges_local = lne;
 
     const auto t_setup0 = std::chrono::steady_clock::now();
@@ -2449,6 +2472,8 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         auto launch_sweep = [&](auto mr_tag, auto slots_tag, auto unit_tag,
                                 i64 s0, i64 s1) {
             constexpr int S = decltype(slots_tag)::value; // 12 B/lane LDS
+            e->sweep.general++;
+            e->sweep.general_slots[mv_sweep_slot_index(S)]++;
             k4_sweep<decltype(mr_tag)::value, S, decltype(unit_tag)::value>
                 <<<range_grid(s0, s1), 256, S * 256 * 12, st>>>(
                     s0, s1, lnv, e->base, e->d_perm, e->d_deg,
@@ -2476,6 +2501,8 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         };
         auto launch_iter1 = [&](auto mr_tag, auto unit_tag, auto lblasc_tag,
                                 i64 s0, i64 s1) {
+            if (decltype(lblasc_tag)::value) e->sweep.iter1_label_order++;
+            else e->sweep.iter1_internal_order++;
             k4_sweep_iter1<decltype(mr_tag)::value, decltype(unit_tag)::value,
                            decltype(lblasc_tag)::value>
                 <<<range_grid(s0, s1), 256, 0, st>>>(
@@ -2493,6 +2520,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                                          8 * e->hash_hub_elems, st));
             if (e->nlh > e->nhi) // per-lane hash band [nhi, nlh)
                 by_flag(e->unit_weights, [&](auto unit_tag) {
+                    e->sweep.lh++;
                     k4_sweep_lh<decltype(unit_tag)::value>
                         <<<grid_for(e->nlh - e->nhi), 256, 0, st>>>(
                             e->nhi, e->nlh, lnv, e->base, e->d_perm,
@@ -2505,6 +2533,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                 });
             if (e->nhi > 0) // wave-per-vertex hubs [0, nhi)
                 by_flag(p > 1, [&](auto mr_tag) {
+                    e->sweep.hi++;
                     k4_sweep_hi<decltype(mr_tag)::value>
                         <<<grid_for(e->nhi * 64, 256, 2048), 256, 0, st>>>(
                             e->nhi, lnv, e->base, e->d_perm, e->d_deg,
