@@ -168,6 +168,34 @@ typedef struct {
 } mv_sweep_info;
 void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
 
+/* What the halo of the last mv_engine_run put on the wire, per rank (tests
+ * assert on it; nothing here is timed). Host-side counts, zeroed where
+ * mv_sweep_info is (graph load and the start of a run) and taken where
+ * the exchange plan is built, above the transport seam, so RCCL and
+ * loopback report the same numbers. All zero at nranks == 1.
+ * One "exchange" is one halo #1a label exchange: a run of K iterations
+ * makes K of them without the overlap and K+1 with it (the pre-loop one
+ * plus one per iteration, the last being the speculative one past the
+ * exit); candidate discovery (prep_calls) follows every exchange.
+ * The send_ / recv_ counters count (peer, exchange) pairs whose segment is
+ * non-empty, by the arm the plan took: the whole segment, (index, label)
+ * pairs of the changed entries, or nothing (no entry changed). The whole
+ * segment goes when changed*12 >= segment*8. With MV_NO_DELTA every
+ * non-empty segment is full. */
+typedef struct {
+    int64_t exchanges;
+    int64_t send_full, send_compact, send_silent;
+    int64_t recv_full, recv_compact, recv_silent;
+    int64_t send_compact_entries; /* (index, label) pairs sent ... */
+    int64_t recv_compact_entries; /* ... and received */
+    int64_t prep_calls;           /* candidate discoveries */
+    int64_t nrc_sum;  /* remote communities requested, summed over them */
+    int64_t nrc_max;  /* ... the largest request of one discovery */
+    int64_t nrc_zero; /* ... discoveries that requested none */
+    int64_t nreq_sum; /* records the peers requested from this rank */
+} mv_halo_info;
+void mv_engine_get_halo_info(const mv_engine *e, mv_halo_info *out);
+
 /* ---- beyond phase one: assignment, aggregation, multi-phase driver ----
  * The reference mini-app stops after one phase and never hands the
  * assignment out (main.cpp:164-196 prints modularity and iterations only);

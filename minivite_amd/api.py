@@ -50,6 +50,15 @@ class MvSweepInfo(ctypes.Structure):
     ]
 
 
+class MvHaloInfo(ctypes.Structure):
+    _fields_ = [(name, ctypes.c_int64) for name in (
+        "exchanges",
+        "send_full", "send_compact", "send_silent",
+        "recv_full", "recv_compact", "recv_silent",
+        "send_compact_entries", "recv_compact_entries",
+        "prep_calls", "nrc_sum", "nrc_max", "nrc_zero", "nreq_sum")]
+
+
 class MvPhaseInfo(ctypes.Structure):
     _fields_ = [
         ("iters", ctypes.c_int),
@@ -120,6 +129,8 @@ def lib():
         L.mv_engine_get_sweep_info.restype = None
         L.mv_engine_get_sweep_info.argtypes = [vp,
                                                ctypes.POINTER(MvSweepInfo)]
+        L.mv_engine_get_halo_info.restype = None
+        L.mv_engine_get_halo_info.argtypes = [vp, ctypes.POINTER(MvHaloInfo)]
         L.mv_engine_get_communities.restype = ctypes.c_int
         L.mv_engine_get_communities.argtypes = [vp, pi64]
         L.mv_coarsen_csr.restype = vp
@@ -420,6 +431,13 @@ class Engine:
         d = {f: getattr(s, f) for f, _ in s._fields_}
         d["general_slots"] = dict(zip(SWEEP_SLOTS, s.general_slots))
         return d
+
+    def halo_info(self):
+        """What the halo plans of the last run() carried on this rank
+        (mv_halo_info): exchanges, segments per arm, candidate counts."""
+        s = MvHaloInfo()
+        lib().mv_engine_get_halo_info(self.h, ctypes.byref(s))
+        return {f: getattr(s, f) for f, _ in s._fields_}
 
     def destroy(self):
         if getattr(self, "h", None):

@@ -1418,6 +1418,7 @@ struct mv_engine : mv_graph_state {
 
     mv_stats stats{};
     mv_sweep_info sweep{}; // launch counters only; state is read on request
+    mv_halo_info halo{};   // what the halo plans of the last run carried
     std::vector<hipEvent_t> ev_pool;
     int ev_used = 0;
 
@@ -1631,6 +1632,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     HIP_CHECK(hipDeviceSynchronize());
     e->stats = mv_stats{};
     e->sweep = mv_sweep_info{};
+    e->halo = mv_halo_info{};
     e->stats.edges_local = lne;
     return 0;
 }
@@ -1657,6 +1659,10 @@ void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out) {
     out->rows_sorted = e->rows_sorted;
     out->sell_sorted = e->sell_sorted;
     out->unit_weights = e->unit_weights;
+}
+
+void mv_engine_get_halo_info(const mv_engine *e, mv_halo_info *out) {
+    *out = e->halo;
 }
 
 // ------------------------------------------------------------------------
@@ -2038,9 +2044,15 @@ static void build_sell(mv_engine *e) {
 static void run_halo1a(mv_engine *e, const i64 *commArr, ncclComm_t comm,
                        hipStream_t st2) {
     const int p = e->nranks;
+    e->halo.exchanges++;
     k8_gather_comms<<<grid_for(std::max<i64>(e->ssz, 1)), 256, 0, st2>>>(
         e->ssz, e->d_svdata_int, commArr, e->d_scdata);
     if (!e->use_delta) {
+        for (int r = 0; r < p; r++) { // every non-empty segment goes whole
+            if (r == e->rank) continue;
+            if (e->send_off[r + 1] > e->send_off[r]) e->halo.send_full++;
+            if (e->recv_off[r + 1] > e->recv_off[r]) e->halo.recv_full++;
+        }
         alltoallv(e, e->d_scdata, e->send_off.data(), e->d_ghost_labels,
                   e->recv_off.data(), 8, ncclInt64, comm, st2);
     } else {
@@ -2059,25 +2071,42 @@ static void run_halo1a(mv_engine *e, const i64 *commArr, ncclComm_t comm,
             return changed * 12 >= seg * 8;
         };
         // one direction of the plan for peer r: the whole segment, or the
-        // (chg_idx, chg_lab) pair of its changed entries, or nothing
+        // (chg_idx, chg_lab) pair of its changed entries, or nothing; the
+        // arm taken is counted for mv_halo_info
+        struct ArmCounts {
+            int64_t &full, &compact, &silent, &entries;
+        };
         auto plan = [&](std::vector<Xfer> &out, int r, i64 off, i64 seg,
-                        i64 chg, i64 *full, unsigned *idx, i64 *lab) {
+                        i64 chg, i64 *full, unsigned *idx, i64 *lab,
+                        ArmCounts n) {
             if (full_mode(chg, seg)) {
-                if (seg > 0) out.push_back({r, full + off, ncclInt64, seg});
+                if (seg > 0) {
+                    out.push_back({r, full + off, ncclInt64, seg});
+                    n.full++;
+                }
             } else if (chg > 0) {
                 out.push_back({r, idx + off, ncclChar, chg * 4});
                 out.push_back({r, lab + off, ncclInt64, chg});
+                n.compact++;
+                n.entries += chg;
+            } else {
+                n.silent++; // seg > 0 here: an empty segment is full_mode
             }
         };
+        mv_halo_info &h = e->halo;
+        const ArmCounts nsend{h.send_full, h.send_compact, h.send_silent,
+                              h.send_compact_entries};
+        const ArmCounts nrecv{h.recv_full, h.recv_compact, h.recv_silent,
+                              h.recv_compact_entries};
         std::vector<Xfer> sends, recvs;
         for (int r = 0; r < p; r++) {
             if (r == e->rank) continue;
             plan(sends, r, e->send_off[r], e->send_off[r + 1] - e->send_off[r],
                  e->h_cntmat[(i64)e->rank * p + r], e->d_scdata, e->d_chg_idx,
-                 e->d_chg_lab);
+                 e->d_chg_lab, nsend);
             plan(recvs, r, e->recv_off[r], e->recv_off[r + 1] - e->recv_off[r],
                  e->h_cntmat[(i64)r * p + e->rank], e->d_ghost_labels,
-                 e->d_rchg_idx, e->d_rchg_lab);
+                 e->d_rchg_idx, e->d_rchg_lab, nrecv);
         }
         exchange(e, sends, recvs, comm, st2);
         for (int r = 0; r < p; r++) { // scatter compact segments
@@ -2166,6 +2195,11 @@ static void halo_prep(mv_engine *e, const i64 *curr,
         req_off[r + 1] =
             req_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
     const i64 nreq = req_off[p];
+    e->halo.prep_calls++;
+    e->halo.nrc_sum += nrc;
+    e->halo.nrc_max = std::max<int64_t>(e->halo.nrc_max, nrc);
+    if (nrc == 0) e->halo.nrc_zero++;
+    e->halo.nreq_sum += nreq;
     if (nreq > e->d_req_ids.cap) { // rare growth; device-wide hipFree sync
                                    // is ok
         e->d_req_ids.reserve(std::max<i64>(nreq, 64));
@@ -2323,6 +2357,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
     e->ev_used = 0;
     e->stats = mv_stats{};
     e->sweep = mv_sweep_info{};
+    e->halo = mv_halo_info{};
     e->stats.edges_local = lne;
 
     const auto t_setup0 = std::chrono::steady_clock::now();
