@@ -68,6 +68,10 @@ int64_t mv_graph_nv(const mv_graph *g);
 int64_t mv_graph_lnv(const mv_graph *g);
 int64_t mv_graph_lne(const mv_graph *g);
 const int64_t *mv_graph_parts(const mv_graph *g); /* nranks+1 */
+/* The rank and rank count the slice was built for (no reference
+ * counterpart: there the Graph shares the communicator's). */
+int mv_graph_rank(const mv_graph *g);
+int mv_graph_nranks(const mv_graph *g);
 const int64_t *mv_graph_xadj(const mv_graph *g);  /* lnv+1 */
 const int64_t *mv_graph_tails(const mv_graph *g); /* lne */
 const double *mv_graph_weights(const mv_graph *g);/* lne */
@@ -236,7 +240,8 @@ mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
  * The driver loads g itself and LEAVES THE ENGINE HOLDING THE LAST GRAPH
  * IT LOADED (a device copy of the last level, or of g): call
  * mv_engine_load_graph again before a plain mv_engine_run. Returns NULL
- * with a message on stderr, before any communication, when nranks > 1. */
+ * with a message on stderr, before any communication, when nranks > 1
+ * (mv_engine_run_multiphase_dist below is the driver for that). */
 typedef struct mv_hierarchy mv_hierarchy;
 typedef struct { int iters; double run_mod; int64_t nv_in, ne_in;
                  double run_ms, coarsen_ms; int kept; } mv_phase_info;
@@ -267,6 +272,51 @@ int  mv_hierarchy_phase_proposal(const mv_hierarchy *h, int phase,
  * in [0, nv of level L) (the identity when L == 0). */
 const int64_t *mv_hierarchy_communities(const mv_hierarchy *h);
 void mv_hierarchy_free(mv_hierarchy *h);
+
+/* ---- the same two steps across ranks ----
+ * The coarse graph of a partitioned level is the coarse graph of the
+ * stitched level (dense ids in ascending global label order, one entry per
+ * distinct pair, tails ascending), split evenly: coarse vertex c belongs to
+ * rank r with parts'[r] = (nc * r) / nranks <= c < parts'[r + 1]. A rank
+ * may own no vertices (nc < nranks); such a slice loads and runs like any
+ * other. A coarse weight is the sum, in ascending rank order, of the
+ * per-rank partial sums, each taken in the rank's local edge order with
+ * the fixed-order reduction of mv_coarsen_csr (a pair with partials from
+ * more than 32 ranks is summed by that reduction's fixed tree over the
+ * rank-ordered partials instead of left to right): no floating-point atomics,
+ * bit-identical run to run, exact for integer-valued weights, and at
+ * nranks == 1 bit-identical to mv_coarsen_csr. */
+
+/* Collective. Aggregate the partitioned graph (this rank's slice g) by
+ * comm[lnv] (global labels in [0,nv)). Returns this rank's slice of the
+ * coarse graph (parts = the even split above); map_out[lnv] receives the
+ * global dense coarse id of each local vertex. NULL on EVERY rank if any
+ * rank saw an error (a label out of range, a graph that is not this rank's
+ * slice, nv >= 2^31, or 2^31 - 1 or more local edges or received partial
+ * edges on some rank). Needs no mv_engine_run and leaves the loaded graph
+ * alone. */
+mv_graph *mv_engine_coarsen_dist(mv_engine *e, const mv_graph *g,
+                                 const int64_t *comm, int64_t *map_out);
+
+/* Collective. The multi-phase driver at any nranks (nranks == 1 included,
+ * where it equals mv_engine_run_multiphase bit for bit). The driver rule
+ * is unchanged; "merges nothing" means global nc == global nv, and q of a
+ * level is reduced from per-rank (selfloops, deg^2, W) in rank order, so
+ * every rank takes the same keep / drop / stop decision. The engine is
+ * left holding the last level it loaded. The mv_hierarchy_* accessors
+ * take a per-rank meaning:
+ *  - mv_hierarchy_graph(h, k) is this rank's slice of level k; its parts
+ *    say who owns what;
+ *  - mv_hierarchy_map(h, k) has one entry per vertex of this rank's slice
+ *    of level k-1 (of g for k = 1), values are global ids of level k;
+ *  - mv_hierarchy_communities(h) has one final global dense id per local
+ *    vertex of g (the vertex's own global id when no level was kept);
+ *  - mv_hierarchy_modularity, _phases, _levels, _phase_info (nv_in and
+ *    ne_in are global counts) and _phase_proposal return the same values
+ *    on every rank (wall times excepted). */
+mv_hierarchy *mv_engine_run_multiphase_dist(mv_engine *e, const mv_graph *g,
+                                            double lower, double thresh,
+                                            int max_phases);
 
 #ifdef __cplusplus
 }

@@ -102,6 +102,9 @@ def lib():
         for name in ("mv_graph_parts", "mv_graph_xadj", "mv_graph_tails"):
             getattr(L, name).restype = pi64
             getattr(L, name).argtypes = [vp]
+        for name in ("mv_graph_rank", "mv_graph_nranks"):
+            getattr(L, name).restype = ctypes.c_int
+            getattr(L, name).argtypes = [vp]
         L.mv_graph_weights.restype = pf64
         L.mv_graph_weights.argtypes = [vp]
         L.mv_comm_id.restype = ctypes.c_int
@@ -137,6 +140,11 @@ def lib():
         L.mv_coarsen_csr.argtypes = [ctypes.c_int, vp, pi64, pi64]
         L.mv_engine_run_multiphase.restype = vp
         L.mv_engine_run_multiphase.argtypes = [vp, vp, f64, f64, ctypes.c_int]
+        L.mv_engine_coarsen_dist.restype = vp
+        L.mv_engine_coarsen_dist.argtypes = [vp, vp, pi64, pi64]
+        L.mv_engine_run_multiphase_dist.restype = vp
+        L.mv_engine_run_multiphase_dist.argtypes = [vp, vp, f64, f64,
+                                                    ctypes.c_int]
         for name in ("mv_hierarchy_phases", "mv_hierarchy_levels"):
             getattr(L, name).restype = ctypes.c_int
             getattr(L, name).argtypes = [vp]
@@ -221,6 +229,17 @@ class Graph:
     def lne(self):
         return lib().mv_graph_lne(self.h)
 
+    @property
+    def parts(self):
+        """Ownership bounds of the 1-D partition (read-only copy): rank r
+        owns the global ids [parts[r], parts[r+1]). Its length is the rank
+        count the graph was built for, plus one."""
+        n = lib().mv_graph_nranks(self.h)
+        a = np.ctypeslib.as_array(lib().mv_graph_parts(self.h),
+                                  (n + 1,)).copy()
+        a.flags.writeable = False
+        return a
+
     def arrays(self):
         lnv, lne = self.lnv, self.lne
         xadj = np.ctypeslib.as_array(lib().mv_graph_xadj(self.h), (lnv + 1,)).copy()
@@ -266,7 +285,7 @@ class Hierarchy:
 
     def __init__(self, handle, nv0):
         self.h = handle
-        self._nv0 = nv0
+        self._nv0 = nv0  # vertices of g this rank owns (all of them at p=1)
 
     @property
     def phases(self):
@@ -285,10 +304,12 @@ class Hierarchy:
 
     def map(self, level):
         """Dense map from level-1 vertices to level vertices."""
-        p = lib().mv_hierarchy_map(self.h, level)
-        if not p:
+        if not 1 <= level <= self.levels:
             raise IndexError(f"level {level} not in 1..{self.levels}")
-        n = self._nv0 if level == 1 else self.graph(level - 1).nv
+        n = self._nv0 if level == 1 else self.graph(level - 1).lnv
+        if n == 0:  # this rank owns nothing there: the pointer may be NULL
+            return np.zeros(0, dtype=np.int64)
+        p = lib().mv_hierarchy_map(self.h, level)
         return np.ctypeslib.as_array(p, (n,)).copy()
 
     def modularity(self, level):
@@ -313,6 +334,8 @@ class Hierarchy:
 
     @property
     def communities(self):
+        if self._nv0 == 0:  # a rank without vertices
+            return np.zeros(0, dtype=np.int64)
         p = lib().mv_hierarchy_communities(self.h)
         return np.ctypeslib.as_array(p, (self._nv0,)).copy()
 
@@ -417,6 +440,42 @@ class Engine:
         self._lnv = hier.phase_info(hier.phases)["nv_in"]  # last load
         self._trace_buf = None  # the loads dropped any armed trace
         return hier
+
+    def run_multiphase_dist(self, graph, lower=-1.0, thresh=1e-6,
+                            max_phases=0):
+        """Multi-phase Louvain on the partitioned graph whose slice of
+        this rank is `graph`. Collective: every rank calls it together. The
+        Hierarchy is this rank's view (slices, local maps, local
+        communities; see mv_engine_run_multiphase_dist). The engine is left
+        holding the last level it loaded."""
+        h = lib().mv_engine_run_multiphase_dist(self.h, graph.h, lower,
+                                                thresh, max_phases)
+        if not h:
+            raise RuntimeError("mv_engine_run_multiphase_dist failed")
+        hier = Hierarchy(h, graph.lnv)
+        # phase P ran on level P-1, the last graph the driver loaded
+        last = hier.phases - 1
+        self._lnv = graph.lnv if last == 0 else hier.graph(last).lnv
+        self._trace_buf = None  # the loads dropped any armed trace
+        return hier
+
+    def coarsen_dist(self, graph, comm):
+        """Aggregate the partitioned graph (this rank's slice `graph`) by
+        the global labels `comm` (one per local vertex, values in [0, nv)).
+        Collective. Returns (this rank's slice of the coarse Graph, global
+        coarse id of each local vertex); raises on every rank when any rank
+        saw an error."""
+        comm = np.ascontiguousarray(comm, dtype=np.int64)
+        if comm.shape != (graph.lnv,):
+            raise ValueError("comm must hold one label per local vertex")
+        cmap = np.empty(graph.lnv, dtype=np.int64)
+        h = lib().mv_engine_coarsen_dist(self.h, graph.h, _i64p(comm),
+                                         _i64p(cmap))
+        if not h:
+            raise RuntimeError("mv_engine_coarsen_dist failed on some rank "
+                               "(label out of range, not this rank's slice, "
+                               "or a size limit)")
+        return Graph(h), cmap
 
     def stats(self):
         s = MvStats()

@@ -31,4 +31,75 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
 
 void mv_coarse_dev_free(mv_coarse_dev *c);
 
+// ---- building blocks shared with the distributed aggregation ----
+// Everything below is transport-free: engine.hip strings the pieces
+// together across the exchange seam. Each call works on `st`; the ones
+// that return host values or device allocations synchronise it.
+
+// One (key, summed weight) per distinct key, keys ascending.
+struct mv_key_runs {
+    int64_t n = 0;
+    uint64_t *d_key = nullptr; // never null after the call
+    double *d_w = nullptr;
+};
+void mv_key_runs_free(mv_key_runs *r);
+
+// Stable radix sort of n (key, weight) pairs over the low `bits` key bits,
+// run heads, and the fixed-order run reduction (<= 32 entries left to
+// right by one thread, longer runs by one block's fixed tree): no
+// floating-point atomics, bit-identical run to run. d_w null = every
+// weight is 1 and a run's weight is its length. 0 <= n < 2^31 - 1; the
+// inputs are not modified.
+void mv_sort_reduce_keys(hipStream_t st, int64_t n, const uint64_t *d_keys,
+                         const double *d_w, int bits, mv_key_runs *out);
+
+// Sorted distinct values of n non-negative ids (< 2^bits) plus the way
+// back: input position d_perm[i] holds the id of run d_run[i].
+struct mv_unique_ids {
+    int64_t n = 0, nuniq = 0;
+    int64_t *d_uniq = nullptr; // nuniq ids, ascending
+    unsigned *d_perm = nullptr; // n: sorted position -> input position
+    unsigned *d_run = nullptr;  // n: sorted position -> index into d_uniq
+};
+void mv_unique_ids_free(mv_unique_ids *u);
+void mv_sort_unique_ids(hipStream_t st, int64_t n, const int64_t *d_ids,
+                        int bits, mv_unique_ids *out);
+// d_out[input position] = d_vals[index of its id in d_uniq]
+void mv_scatter_unique(hipStream_t st, const mv_unique_ids *u,
+                       const int64_t *d_vals, int64_t *d_out);
+
+// h_out[j] = first index of d_sorted[0,n) whose value is >= h_keys[j]
+// (owner buckets of sorted ids or keys); host in, host out.
+void mv_lower_bounds(hipStream_t st, const uint64_t *d_sorted, int64_t n,
+                     const uint64_t *h_keys, int m, int64_t *h_out);
+
+// owner side: d_out[k] = d_table[d_ids[k] - base]
+void mv_gather_owned(hipStream_t st, int64_t n, const int64_t *d_ids,
+                     int64_t base, const int64_t *d_table, int64_t *d_out);
+// renumbering: copy labels (one outside [0,nv) raises *d_err and becomes
+// 0), mark the owned labels in use, dense id = offset + rank in use
+void mv_check_labels(hipStream_t st, int64_t n, const int64_t *d_labels,
+                     int64_t nv, int64_t *d_out, unsigned *d_err);
+void mv_mark_owned(hipStream_t st, int64_t n, const int64_t *d_ids,
+                   int64_t base, unsigned *d_used);
+void mv_exclusive_sum_u32(hipStream_t st, const unsigned *d_in,
+                          unsigned *d_out, int64_t n); // 1 <= n < 2^31
+void mv_dense_ids(hipStream_t st, int64_t n, const unsigned *d_rank,
+                  int64_t offset, int64_t *d_dense);
+
+// (map[row] << shift) | coarse id of the tail, per local edge of a slice
+// owning [base,bound): local tails read d_map, remote ones d_ghost_map at
+// their position in the sorted distinct d_ghost_ids.
+void mv_coarse_keys_dist(hipStream_t st, int64_t lnv, int64_t lne,
+                         const int64_t *d_xadj, const int64_t *d_tails,
+                         int64_t base, int64_t bound, const int64_t *d_map,
+                         const int64_t *d_ghost_ids, int64_t nghost,
+                         const int64_t *d_ghost_map, int shift,
+                         uint64_t *d_keys);
+// offsets of rows row0 .. row0+nrows (nrows+1 values, relative to the
+// first run) and the tails of sorted distinct keys
+void mv_coarse_rows(hipStream_t st, int64_t row0, int64_t nrows,
+                    int64_t nruns, int shift, const uint64_t *d_run_key,
+                    int64_t *d_cxadj, int64_t *d_ctails);
+
 #endif

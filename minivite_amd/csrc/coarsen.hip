@@ -22,6 +22,16 @@
 //                 are bit-identical run to run. Unit inputs take the run
 //                 length as the weight.
 // Temporary storage is O(lne).
+//
+// Steps 3 and 4 are one building block (mv_sort_reduce_keys) over a
+// caller-supplied key/weight array. The distributed aggregation (the
+// orchestration and every exchange live in engine.hip, next to the
+// transport seam) runs it twice — once over the local edges, once at the
+// owner over the received per-rank partials — around the transport-free
+// pieces at the end of this file: sort-unique of global ids with the
+// scatter back through the sort permutation, owner-bucket bounds, the
+// owner-side gather / mark / dense-id kernels, and the key kernel with the
+// local / remote tail split.
 
 #include <algorithm>
 #include <cstdint>
@@ -155,9 +165,10 @@ __global__ void k_run_fill(i64 lne, const u64 *__restrict__ ks,
     }
 }
 
-// coarse row offsets (first run whose high key half is >= c) and tails
-// (the low key half of each run)
-__global__ void k_coarse_rows(i64 nc, i64 nruns, int shift,
+// coarse row offsets (first run whose high key half is >= row0 + c, c in
+// [0, nc]) and tails (the low key half of each run); row0 = 0 and nc = all
+// rows on a single rank, the owned range of a partitioned level
+__global__ void k_coarse_rows(i64 row0, i64 nc, i64 nruns, int shift,
                               const u64 *__restrict__ run_key,
                               i64 *__restrict__ cxadj,
                               i64 *__restrict__ ctails) {
@@ -166,7 +177,7 @@ __global__ void k_coarse_rows(i64 nc, i64 nruns, int shift,
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
          i += (i64)gridDim.x * blockDim.x) {
         if (i <= nc) {
-            const u64 key = (u64)i << shift;
+            const u64 key = (u64)(row0 + i) << shift;
             i64 lo = 0, hi = nruns;
             while (lo < hi) {
                 const i64 mid = (lo + hi) >> 1;
@@ -245,6 +256,74 @@ void exclusive_sum(hipStream_t st, const unsigned *in, unsigned *out, i64 n) {
 
 } // namespace
 
+void mv_key_runs_free(mv_key_runs *r) {
+    if (r->d_key) (void)hipFree(r->d_key);
+    if (r->d_w) (void)hipFree(r->d_w);
+    *r = mv_key_runs{};
+}
+
+void mv_sort_reduce_keys(hipStream_t st, int64_t n, const uint64_t *d_keys_in,
+                         const double *d_w, int bits, mv_key_runs *out) {
+    *out = mv_key_runs{};
+    if (n == 0) { // never-null outputs, no zero-length hipCUB calls
+        HIP_CHECK(hipMalloc((void **)&out->d_key, 8));
+        HIP_CHECK(hipMalloc((void **)&out->d_w, 8));
+        return;
+    }
+    const u64 *keys = (const u64 *)d_keys_in;
+    // ---- 3. sort over the live key bits ----
+    Scratch<u64> ks(n);
+    Scratch<double> ws(d_w ? n : 0);
+    {
+        size_t bytes = 0;
+        if (d_w)
+            (void)hipcub::DeviceRadixSort::SortPairs(
+                nullptr, bytes, keys, ks.ptr, d_w, ws.ptr, (int)n, 0, bits,
+                st);
+        else
+            (void)hipcub::DeviceRadixSort::SortKeys(
+                nullptr, bytes, keys, ks.ptr, (int)n, 0, bits, st);
+        Scratch<char> tmp((i64)bytes);
+        if (d_w)
+            HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
+                tmp.ptr, bytes, keys, ks.ptr, d_w, ws.ptr, (int)n, 0, bits,
+                st));
+        else
+            HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(
+                tmp.ptr, bytes, keys, ks.ptr, (int)n, 0, bits, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+
+    // ---- 4. runs ----
+    Scratch<unsigned> head(n + 1), pos(n + 1);
+    k_run_heads<<<grid_for(n + 1), 256, 0, st>>>(n, ks, head);
+    exclusive_sum(st, head, pos, n + 1);
+    unsigned h_runs = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_runs, pos + n, 4, hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    const i64 nruns = h_runs;
+    out->n = nruns;
+    HIP_CHECK(hipMalloc((void **)&out->d_key, 8 * nruns));
+    HIP_CHECK(hipMalloc((void **)&out->d_w, 8 * nruns));
+    Scratch<i64> run_start(nruns + 1);
+    k_run_fill<<<grid_for(n + 1), 256, 0, st>>>(n, ks, head, pos, run_start,
+                                                (u64 *)out->d_key);
+    if (!d_w) {
+        k_run_lengths<<<grid_for(nruns), 256, 0, st>>>(nruns, run_start,
+                                                       out->d_w);
+        HIP_CHECK(hipStreamSynchronize(st));
+    } else {
+        Scratch<i64> long_list(nruns);
+        Scratch<u64> long_count(1);
+        HIP_CHECK(hipMemsetAsync(long_count, 0, 8, st));
+        k_reduce_short<<<grid_for(nruns), 256, 0, st>>>(
+            nruns, run_start, ws, out->d_w, long_list, long_count);
+        k_reduce_long<<<grid_for(nruns, 1, 1024), 256, 0, st>>>(
+            long_list, long_count, run_start, ws, out->d_w);
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+}
+
 void mv_coarse_dev_free(mv_coarse_dev *c) {
     if (c->d_map) (void)hipFree(c->d_map);
     if (c->d_xadj) (void)hipFree(c->d_xadj);
@@ -301,63 +380,22 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
         HIP_CHECK(hipStreamSynchronize(st));
         return 0;
     }
-    Scratch<u64> keys(lne), ks(lne);
-    Scratch<double> ws(d_w ? lne : 0);
+    Scratch<u64> keys(lne);
     k_coarse_keys<<<grid_for(lne), 256, 0, st>>>(nv, lne, d_xadj, d_tails,
                                                  out->d_map, shift, keys);
-    {
-        size_t bytes = 0;
-        if (d_w)
-            (void)hipcub::DeviceRadixSort::SortPairs(
-                nullptr, bytes, keys.ptr, ks.ptr, d_w, ws.ptr, (int)lne, 0,
-                2 * shift, st);
-        else
-            (void)hipcub::DeviceRadixSort::SortKeys(
-                nullptr, bytes, keys.ptr, ks.ptr, (int)lne, 0, 2 * shift, st);
-        Scratch<char> tmp((i64)bytes);
-        if (d_w)
-            HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-                tmp.ptr, bytes, keys.ptr, ks.ptr, d_w, ws.ptr, (int)lne, 0,
-                2 * shift, st));
-        else
-            HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(
-                tmp.ptr, bytes, keys.ptr, ks.ptr, (int)lne, 0, 2 * shift,
-                st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
-
-    // ---- 4. runs ----
-    Scratch<unsigned> head(lne + 1), pos(lne + 1);
-    k_run_heads<<<grid_for(lne + 1), 256, 0, st>>>(lne, ks, head);
-    exclusive_sum(st, head, pos, lne + 1);
-    unsigned h_runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_runs, pos + lne, 4, hipMemcpyDeviceToHost,
-                             st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const i64 nruns = h_runs;
+    mv_key_runs runs;
+    mv_sort_reduce_keys(st, lne, (const uint64_t *)keys.ptr, d_w, 2 * shift,
+                        &runs);
+    const i64 nruns = runs.n;
     out->ne = nruns;
-    HIP_CHECK(hipMalloc((void **)&out->d_tails, 8 * nruns));
-    HIP_CHECK(hipMalloc((void **)&out->d_w, 8 * nruns));
-    Scratch<i64> run_start(nruns + 1);
-    Scratch<u64> run_key(nruns);
-    k_run_fill<<<grid_for(lne + 1), 256, 0, st>>>(lne, ks, head, pos,
-                                                  run_start, run_key);
+    HIP_CHECK(hipMalloc((void **)&out->d_tails, 8 * std::max<i64>(nruns, 1)));
     k_coarse_rows<<<grid_for(std::max(nruns, nc + 1)), 256, 0, st>>>(
-        nc, nruns, shift, run_key, out->d_xadj, out->d_tails);
-    if (!d_w) {
-        k_run_lengths<<<grid_for(nruns), 256, 0, st>>>(nruns, run_start,
-                                                       out->d_w);
-        HIP_CHECK(hipStreamSynchronize(st));
-    } else {
-        Scratch<i64> long_list(nruns);
-        Scratch<u64> long_count(1);
-        HIP_CHECK(hipMemsetAsync(long_count, 0, 8, st));
-        k_reduce_short<<<grid_for(nruns), 256, 0, st>>>(
-            nruns, run_start, ws, out->d_w, long_list, long_count);
-        k_reduce_long<<<grid_for(nruns, 1, 1024), 256, 0, st>>>(
-            long_list, long_count, run_start, ws, out->d_w);
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
+        0, nc, nruns, shift, (const u64 *)runs.d_key, out->d_xadj,
+        out->d_tails);
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->d_w = runs.d_w; // the run weights ARE the coarse weights
+    runs.d_w = nullptr;
+    mv_key_runs_free(&runs);
     return 0;
 }
 
@@ -427,4 +465,251 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
                                      ct.data(), cw.data());
     mv_coarse_dev_free(&c);
     return cg;
+}
+
+// ------------------------------------------------------------------------
+// Transport-free pieces of the distributed aggregation (engine.hip strings
+// them together across the seam; DESIGN.md, multi-phase section).
+
+namespace {
+
+// first index in sorted[0,n) whose value is >= key
+__device__ __forceinline__ i64 lower_bound_u64(const u64 *__restrict__ a,
+                                               i64 n, u64 key) {
+    i64 lo = 0, hi = n;
+    while (lo < hi) {
+        const i64 mid = (lo + hi) >> 1;
+        if (a[mid] < key) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+__global__ void k_lower_bounds(const u64 *__restrict__ sorted, i64 n,
+                               const u64 *__restrict__ keys, int m,
+                               i64 *__restrict__ out) {
+    const int j = blockIdx.x * blockDim.x + threadIdx.x;
+    if (j < m) out[j] = lower_bound_u64(sorted, n, keys[j]);
+}
+
+__global__ void k_iota_u32(i64 n, unsigned *__restrict__ out) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
+         i += (i64)gridDim.x * blockDim.x)
+        out[i] = (unsigned)i;
+}
+
+// heads of the runs of equal sorted ids; head[n] = 0 closes the scan
+__global__ void k_id_heads(i64 n, const i64 *__restrict__ s,
+                           unsigned *__restrict__ head) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i <= n;
+         i += (i64)gridDim.x * blockDim.x)
+        head[i] = (i < n && (i == 0 || s[i] != s[i - 1])) ? 1u : 0u;
+}
+
+// run[i] = index of sorted entry i's run; uniq[run] = the id at its head
+__global__ void k_id_runs(i64 n, const i64 *__restrict__ s,
+                          const unsigned *__restrict__ head,
+                          const unsigned *__restrict__ pos,
+                          unsigned *__restrict__ run,
+                          i64 *__restrict__ uniq) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
+         i += (i64)gridDim.x * blockDim.x) {
+        const unsigned r = pos[i] + head[i] - 1u;
+        run[i] = r;
+        if (head[i]) uniq[r] = s[i];
+    }
+}
+
+__global__ void k_scatter_unique(i64 n, const unsigned *__restrict__ perm,
+                                 const unsigned *__restrict__ run,
+                                 const i64 *__restrict__ vals,
+                                 i64 *__restrict__ out) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
+         i += (i64)gridDim.x * blockDim.x)
+        out[perm[i]] = vals[run[i]];
+}
+
+__global__ void k_gather_owned(i64 n, const i64 *__restrict__ ids, i64 base,
+                               const i64 *__restrict__ table,
+                               i64 *__restrict__ out) {
+    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < n;
+         k += (i64)gridDim.x * blockDim.x)
+        out[k] = table[ids[k] - base];
+}
+
+// labels outside [0,nv) raise *err and are passed on as 0 so that the
+// sort and the owner buckets stay inside the id range
+__global__ void k_check_labels(i64 n, const i64 *__restrict__ labels, i64 nv,
+                               i64 *__restrict__ out,
+                               unsigned *__restrict__ err) {
+    for (i64 v = blockIdx.x * (i64)blockDim.x + threadIdx.x; v < n;
+         v += (i64)gridDim.x * blockDim.x) {
+        const i64 l = labels[v];
+        const bool bad = l < 0 || l >= nv;
+        if (bad) *err = 1u;
+        out[v] = bad ? 0 : l;
+    }
+}
+
+__global__ void k_mark_owned(i64 n, const i64 *__restrict__ ids, i64 base,
+                             unsigned *__restrict__ used) {
+    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < n;
+         k += (i64)gridDim.x * blockDim.x)
+        used[ids[k] - base] = 1u;
+}
+
+__global__ void k_dense_ids(i64 n, const unsigned *__restrict__ rank,
+                            i64 offset, i64 *__restrict__ dense) {
+    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
+         i += (i64)gridDim.x * blockDim.x)
+        dense[i] = offset + (i64)rank[i];
+}
+
+// k_coarse_keys over one rank's slice: rows are local (map holds the lnv
+// owned vertices), a tail inside [base,bound) reads map directly and a
+// remote one the value fetched for it (ghost_ids sorted unique, ghost_map
+// aligned with it)
+__global__ __launch_bounds__(256) void k_coarse_keys_dist(
+    i64 lnv, i64 lne, const i64 *__restrict__ xadj,
+    const i64 *__restrict__ tails, i64 base, i64 bound,
+    const i64 *__restrict__ map, const i64 *__restrict__ ghost_ids,
+    i64 nghost, const i64 *__restrict__ ghost_map, int shift,
+    u64 *__restrict__ keys) {
+    const int lane = threadIdx.x & 63;
+    const i64 wave = (blockIdx.x * (i64)blockDim.x + threadIdx.x) >> 6;
+    const i64 nwaves = ((i64)gridDim.x * blockDim.x) >> 6;
+    for (i64 e0 = wave * 64; e0 < lne; e0 += nwaves * 64) {
+        const i64 e1 = e0 + 63 < lne ? e0 + 63 : lne - 1;
+        const i64 r0 = row_of(xadj, 0, lnv - 1, e0);
+        const i64 r1 = row_of(xadj, r0, lnv - 1, e1);
+        const i64 e = e0 + lane;
+        if (e <= e1) {
+            const i64 r = row_of(xadj, r0, r1, e);
+            const i64 t = tails[e];
+            i64 ct;
+            if (t >= base && t < bound) {
+                ct = map[t - base];
+            } else {
+                i64 lo = 0, hi = nghost - 1; // t is in ghost_ids
+                while (lo < hi) {
+                    const i64 mid = (lo + hi) >> 1;
+                    if (ghost_ids[mid] < t) lo = mid + 1;
+                    else hi = mid;
+                }
+                ct = ghost_map[lo];
+            }
+            keys[e] = ((u64)map[r] << shift) | (u64)ct;
+        }
+    }
+}
+
+} // namespace
+
+void mv_unique_ids_free(mv_unique_ids *u) {
+    if (u->d_uniq) (void)hipFree(u->d_uniq);
+    if (u->d_perm) (void)hipFree(u->d_perm);
+    if (u->d_run) (void)hipFree(u->d_run);
+    *u = mv_unique_ids{};
+}
+
+void mv_sort_unique_ids(hipStream_t st, int64_t n, const int64_t *d_ids,
+                        int bits, mv_unique_ids *out) {
+    *out = mv_unique_ids{};
+    out->n = n;
+    HIP_CHECK(hipMalloc((void **)&out->d_uniq, 8 * std::max<i64>(n, 1)));
+    HIP_CHECK(hipMalloc((void **)&out->d_perm, 4 * std::max<i64>(n, 1)));
+    HIP_CHECK(hipMalloc((void **)&out->d_run, 4 * std::max<i64>(n, 1)));
+    if (n == 0) return;
+    Scratch<i64> sorted(n);
+    Scratch<unsigned> iota(n), head(n + 1), pos(n + 1);
+    k_iota_u32<<<grid_for(n), 256, 0, st>>>(n, iota);
+    {
+        size_t bytes = 0;
+        (void)hipcub::DeviceRadixSort::SortPairs(
+            nullptr, bytes, d_ids, sorted.ptr, iota.ptr, out->d_perm, (int)n,
+            0, bits, st);
+        Scratch<char> tmp((i64)bytes);
+        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
+            tmp.ptr, bytes, d_ids, sorted.ptr, iota.ptr, out->d_perm, (int)n,
+            0, bits, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    k_id_heads<<<grid_for(n + 1), 256, 0, st>>>(n, sorted, head);
+    exclusive_sum(st, head, pos, n + 1);
+    unsigned h_n = 0;
+    HIP_CHECK(hipMemcpyAsync(&h_n, pos + n, 4, hipMemcpyDeviceToHost, st));
+    k_id_runs<<<grid_for(n), 256, 0, st>>>(n, sorted, head, pos, out->d_run,
+                                           out->d_uniq);
+    HIP_CHECK(hipStreamSynchronize(st));
+    out->nuniq = h_n;
+}
+
+void mv_scatter_unique(hipStream_t st, const mv_unique_ids *u,
+                       const int64_t *d_vals, int64_t *d_out) {
+    if (u->n == 0) return;
+    k_scatter_unique<<<grid_for(u->n), 256, 0, st>>>(u->n, u->d_perm,
+                                                     u->d_run, d_vals, d_out);
+}
+
+void mv_lower_bounds(hipStream_t st, const uint64_t *d_sorted, int64_t n,
+                     const uint64_t *h_keys, int m, int64_t *h_out) {
+    Scratch<u64> d_keys(m);
+    Scratch<i64> d_out(m);
+    HIP_CHECK(hipMemcpyAsync(d_keys, h_keys, 8 * (size_t)m,
+                             hipMemcpyHostToDevice, st));
+    k_lower_bounds<<<(m + 63) / 64, 64, 0, st>>>((const u64 *)d_sorted, n,
+                                                 d_keys, m, d_out);
+    HIP_CHECK(hipMemcpyAsync(h_out, d_out, 8 * (size_t)m,
+                             hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+void mv_gather_owned(hipStream_t st, int64_t n, const int64_t *d_ids,
+                     int64_t base, const int64_t *d_table, int64_t *d_out) {
+    if (n == 0) return;
+    k_gather_owned<<<grid_for(n), 256, 0, st>>>(n, d_ids, base, d_table,
+                                                d_out);
+}
+
+void mv_check_labels(hipStream_t st, int64_t n, const int64_t *d_labels,
+                     int64_t nv, int64_t *d_out, unsigned *d_err) {
+    if (n == 0) return;
+    k_check_labels<<<grid_for(n), 256, 0, st>>>(n, d_labels, nv, d_out,
+                                                d_err);
+}
+
+void mv_mark_owned(hipStream_t st, int64_t n, const int64_t *d_ids,
+                   int64_t base, unsigned *d_used) {
+    if (n == 0) return;
+    k_mark_owned<<<grid_for(n), 256, 0, st>>>(n, d_ids, base, d_used);
+}
+
+void mv_exclusive_sum_u32(hipStream_t st, const unsigned *d_in,
+                          unsigned *d_out, int64_t n) {
+    exclusive_sum(st, d_in, d_out, n);
+}
+
+void mv_dense_ids(hipStream_t st, int64_t n, const unsigned *d_rank,
+                  int64_t offset, int64_t *d_dense) {
+    if (n == 0) return;
+    k_dense_ids<<<grid_for(n), 256, 0, st>>>(n, d_rank, offset, d_dense);
+}
+
+void mv_coarse_keys_dist(hipStream_t st, int64_t lnv, int64_t lne,
+                         const int64_t *d_xadj, const int64_t *d_tails,
+                         int64_t base, int64_t bound, const int64_t *d_map,
+                         const int64_t *d_ghost_ids, int64_t nghost,
+                         const int64_t *d_ghost_map, int shift,
+                         uint64_t *d_keys) {
+    if (lne == 0) return;
+    k_coarse_keys_dist<<<grid_for(lne), 256, 0, st>>>(
+        lnv, lne, d_xadj, d_tails, base, bound, d_map, d_ghost_ids, nghost,
+        d_ghost_map, shift, (u64 *)d_keys);
+}
+
+void mv_coarse_rows(hipStream_t st, int64_t row0, int64_t nrows,
+                    int64_t nruns, int shift, const uint64_t *d_run_key,
+                    int64_t *d_cxadj, int64_t *d_ctails) {
+    k_coarse_rows<<<grid_for(std::max(nruns, nrows + 1)), 256, 0, st>>>(
+        row0, nrows, nruns, shift, (const u64 *)d_run_key, d_cxadj, d_ctails);
 }

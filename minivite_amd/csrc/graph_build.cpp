@@ -526,6 +526,8 @@ int64_t mv_graph_lnv(const mv_graph *g) {
 }
 int64_t mv_graph_lne(const mv_graph *g) { return (int64_t)g->tails.size(); }
 const int64_t *mv_graph_parts(const mv_graph *g) { return g->parts.data(); }
+int mv_graph_rank(const mv_graph *g) { return g->rank; }
+int mv_graph_nranks(const mv_graph *g) { return g->nranks; }
 const int64_t *mv_graph_xadj(const mv_graph *g) { return g->xadj.data(); }
 const int64_t *mv_graph_tails(const mv_graph *g) { return g->tails.data(); }
 const double *mv_graph_weights(const mv_graph *g) { return g->weights.data(); }
