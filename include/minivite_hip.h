@@ -80,6 +80,26 @@ const double *mv_graph_weights(const mv_graph *g);/* lne */
  * only — results are identical with or without it. */
 const int32_t *mv_graph_locality_hint(const mv_graph *g);
 
+/* Windowed degree order: refine an internal order so that every SELL slice
+ * (64 consecutive positions) holds vertices of nearly equal degree while a
+ * vertex never leaves its window of `window` consecutive positions. Host
+ * only, needs no GPU. hint[k] = local vertex at position k (NULL: the
+ * identity), xadj has lnv+1 entries; out[lnv] receives the refined order.
+ * window: a power of two >= 128; quant >= 1; group: a power of two with
+ * 1 <= group <= window/64. For each aligned window of `window` positions:
+ *  - its vertices are stable-sorted by key (degree + quant - 1) / quant,
+ *    descending, and cut into rows of 64;
+ *  - with R = window/64 rows and G = R/group, sorted row r goes to row
+ *    position (r mod G)*group + r/G, so every aligned run of `group` rows
+ *    samples the window's degree spectrum evenly (G == 1: plain sorted);
+ *  - a short last window (lnv not a multiple of window, or window > lnv)
+ *    keeps the plain sorted order.
+ * Layout metadata only, like the hint. Returns non-zero, writing nothing,
+ * for arguments outside the ranges above. */
+int mv_degree_window_order(const int32_t *hint, const int64_t *xadj,
+                           int64_t lnv, int64_t window, int64_t quant,
+                           int64_t group, int32_t *out);
+
 /* ---- the hot path (replaces distLouvainMethod, dspl.hpp:1280-1441) ---- */
 
 typedef struct mv_engine mv_engine;
@@ -169,6 +189,22 @@ typedef struct {
     int rows_sorted;          /* input rows had ascending tails */
     int sell_sorted;          /* SELL rows re-sorted by internal index */
     int unit_weights;         /* every local edge weight == 1.0 */
+    /* Windowed degree order (mv_degree_window_order), decided at graph
+     * load. It applies only to a graph with a locality hint that is not
+     * skewed. MV_DEG_WINDOW (vertices, a power of two >= 128; 0 = off) and
+     * MV_DEG_QUANT (>= 1) are read at every load. A window set through
+     * MV_DEG_WINDOW is honoured as given — a window longer than lnv is
+     * reported as set and is one short window — with row_group =
+     * min(window/64, 8). Without it the built-in default window applies
+     * and row_group is the largest power of two <= min(window/64, rows per
+     * wave), rows per wave = ceil(ceil(lnv/64) / waves of the full sweep
+     * grid); below 2 the order is off for this graph. Off means
+     * deg_window == 0, deg_quant == 1, row_group == 1. */
+    int64_t deg_window;       /* effective window, vertices (0 = off) */
+    int64_t deg_quant;        /* effective degree quantum */
+    int64_t row_group;        /* rows of 64 positions a wave takes in turn
+                               * in k4_sweep / k4_sweep_iter1 */
+    int64_t sell_entries;     /* SELL image entries, padding included */
 } mv_sweep_info;
 void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
 

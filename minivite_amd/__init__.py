@@ -10,6 +10,7 @@ from .api import (  # noqa: F401
     Engine,
     Hierarchy,
     coarsen_csr,
+    degree_window_order,
     LoopbackSession,
     comm_id,
     lib,

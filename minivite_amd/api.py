@@ -47,6 +47,10 @@ class MvSweepInfo(ctypes.Structure):
         ("rows_sorted", ctypes.c_int),
         ("sell_sorted", ctypes.c_int),
         ("unit_weights", ctypes.c_int),
+        ("deg_window", ctypes.c_int64),
+        ("deg_quant", ctypes.c_int64),
+        ("row_group", ctypes.c_int64),
+        ("sell_entries", ctypes.c_int64),
     ]
 
 
@@ -107,6 +111,12 @@ def lib():
             getattr(L, name).argtypes = [vp]
         L.mv_graph_weights.restype = pf64
         L.mv_graph_weights.argtypes = [vp]
+        pi32 = ctypes.POINTER(ctypes.c_int32)
+        L.mv_graph_locality_hint.restype = pi32
+        L.mv_graph_locality_hint.argtypes = [vp]
+        L.mv_degree_window_order.restype = ctypes.c_int
+        L.mv_degree_window_order.argtypes = [pi32, pi64, i64, i64, i64, i64,
+                                             pi32]
         L.mv_comm_id.restype = ctypes.c_int
         L.mv_comm_id.argtypes = [ctypes.c_void_p]
         L.mv_lb_create.restype = vp
@@ -249,6 +259,13 @@ class Graph:
         w = np.ctypeslib.as_array(lib().mv_graph_weights(self.h), (lne,)).copy()
         return xadj, tails, w
 
+    def locality_hint(self):
+        """The builder's internal-layout hint (copy), or None."""
+        p = lib().mv_graph_locality_hint(self.h)
+        if not p:
+            return None
+        return np.ctypeslib.as_array(p, (self.lnv,)).copy()
+
     def write_binary(self, path):
         if lib().mv_graph_write_binary(self.h, path.encode()) != 0:
             raise RuntimeError("mv_graph_write_binary failed")
@@ -263,6 +280,26 @@ class Graph:
             self.free()
         except Exception:
             pass
+
+
+def degree_window_order(hint, xadj, window, quant=1, group=1):
+    """mv_degree_window_order on the host: the windowed degree order of
+    `hint` (None: the identity) for the CSR row bounds `xadj`."""
+    xadj = np.ascontiguousarray(xadj, dtype=np.int64)
+    lnv = len(xadj) - 1
+    hp = None
+    if hint is not None:
+        hint = np.ascontiguousarray(hint, dtype=np.int32)
+        if hint.shape != (lnv,):
+            raise ValueError("hint must hold one vertex per position")
+        hp = hint.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))
+    out = np.empty(lnv, dtype=np.int32)
+    if lib().mv_degree_window_order(
+            hp, _i64p(xadj), lnv, window, quant, group,
+            out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32))) != 0:
+        raise ValueError("window must be a power of two >= 128, quant >= 1, "
+                         "group a power of two <= window/64")
+    return out
 
 
 def coarsen_csr(graph, comm, device=0):
@@ -385,6 +422,7 @@ class Engine:
             raise RuntimeError(
                 "mv_engine_create failed — an MI355X GPU is required; "
                 "there is no CPU fallback")
+        self.rank = rank
         self._trace_buf = None
 
     @classmethod
@@ -395,6 +433,7 @@ class Engine:
                                           session.h)
         if not obj.h:
             raise RuntimeError("mv_engine_create_lb failed")
+        obj.rank = rank
         obj._trace_buf = None
         return obj
 

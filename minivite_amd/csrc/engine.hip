@@ -776,10 +776,29 @@ __device__ __forceinline__ void wave_reduce_best(double &bg, i64 &bl,
     }
 }
 
+// Row schedule of the lane-per-vertex sweeps (k4_sweep, k4_sweep_iter1).
+// Row r of a launch is positions s_begin + 64r .. + 63, one per lane. Wave
+// x takes rows xS .. xS+S-1 in order, then advances by (waves of the
+// launch) * S rows: with the windowed degree order every wave then walks
+// whole groups of S rows, each a sample of its window's degree spectrum,
+// instead of the same degree rank of every window (a grid stride of 8192
+// waves is a multiple of every window length). S == 1 is the plain grid
+// stride. Everything but s is wave-uniform. row_first: the lane's first
+// position; row_next: the step after a row, r counting the rows done in
+// the current group.
+__device__ __forceinline__ i64 row_first(i64 s_begin, i64 gthread, int S) {
+    return s_begin + (gthread >> 6) * 64 * S + (gthread & 63);
+}
+__device__ __forceinline__ i64 row_next(i64 s, int &r, int S, i64 stride) {
+    if (++r < S) return s + 64;
+    r = 0;
+    return s + 64 + (stride - 64) * S;
+}
+
 // ---- K4 general sweep: LDS slots + spill, any iteration ----
 template <bool MR, int SLOTS, bool UNIT>
 __global__ __launch_bounds__(256) void k4_sweep(
-    i64 s_begin, i64 s_end, i64 lnv, i64 base,
+    i64 s_begin, i64 s_end, int S_rows, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
     const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
@@ -801,7 +820,9 @@ __global__ __launch_bounds__(256) void k4_sweep(
     unsigned *myspill_k = spill_keys + spill_off[gthread];
     double *myspill_a = spill_acc + spill_off[gthread];
 
-    for (i64 s = s_begin + gthread; s < s_end; s += stride) {
+    int rdone = 0;
+    for (i64 s = row_first(s_begin, gthread, S_rows); s < s_end;
+         s = row_next(s, rdone, S_rows, stride)) {
         const i64 i = perm[s];          // internal vertex index
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
@@ -1107,7 +1128,7 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
 // INTERNAL order instead and ties compare the batched labels explicitly.
 template <bool MR, bool UNIT, bool LBL_ASC>
 __global__ __launch_bounds__(256) void k4_sweep_iter1(
-    i64 s_begin, i64 s_end, i64 lnv, i64 base,
+    i64 s_begin, i64 s_end, int S_rows, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
     const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
@@ -1120,7 +1141,9 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1(
     using label = label_t<MR>;
     const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
     const i64 stride = (i64)gridDim.x * blockDim.x;
-    for (i64 s = s_begin + gthread; s < s_end; s += stride) {
+    int rdone = 0;
+    for (i64 s = row_first(s_begin, gthread, S_rows); s < s_end;
+         s = row_next(s, rdone, S_rows, stride)) {
         const i64 i = perm[s];
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
@@ -1319,6 +1342,11 @@ struct mv_graph_state {
     DevBuf<unsigned> d_sigma;     // internal -> original local id
     DevBuf<unsigned> d_sigma_inv; // original local id -> internal
     int has_hint = 0;
+    // windowed degree order folded into sigma at load (0 / 1 / 1 = off) and
+    // the row-group length the lane-per-vertex sweeps run with
+    i64 deg_window = 0, deg_quant = 1;
+    int row_group = 1;
+    i64 sell_entries = 0; // SELL image size, padding included
 
     // SELL-64 image (built in the per-run setup span)
     DevBuf<unsigned> d_deg;          // degree per INTERNAL index
@@ -1537,6 +1565,45 @@ void mv_engine_destroy(mv_engine *e) {
     delete e;
 }
 
+// Default window (vertices; 0 = off) and degree quantum of the windowed
+// degree order: the best pair measured on the bench workload
+// (experiments/RESULTS.md, "windowed degree order").
+constexpr i64 DEG_WINDOW_DEFAULT = 2048;
+constexpr i64 DEG_QUANT_DEFAULT = 4;
+
+// Decide the windowed degree order of this graph (mv_sweep_info documents
+// the rule): needs has_hint, skewed, lnv and sweep_grid. MV_DEG_WINDOW /
+// MV_DEG_QUANT are read at every load (perf only, results identical).
+static void choose_degree_windows(mv_engine *e) {
+    e->deg_window = 0;
+    e->deg_quant = 1;
+    e->row_group = 1;
+    if (!e->has_hint || e->skewed) return;
+    const char *ws = getenv("MV_DEG_WINDOW");
+    const char *qs = getenv("MV_DEG_QUANT");
+    const i64 W = ws ? atoll(ws) : DEG_WINDOW_DEFAULT;
+    const i64 q = qs ? atoll(qs) : DEG_QUANT_DEFAULT;
+    if (W <= 0) return;
+    if (W < 128 || (W & (W - 1)) || q < 1) {
+        std::fprintf(stderr, "MV_DEG_WINDOW must be 0 or a power of two >= "
+                             "128 and MV_DEG_QUANT >= 1: degree windows off\n");
+        return;
+    }
+    i64 S = 1;
+    if (ws) { // an explicit window is honoured even where waves then idle
+        S = std::min<i64>(W / 64, 8);
+    } else {
+        const i64 rows = (e->lnv + 63) / 64;
+        const i64 waves = 4 * (i64)e->sweep_grid;
+        const i64 cap = std::min(W / 64, (rows + waves - 1) / waves);
+        while (S * 2 <= cap) S *= 2;
+        if (S < 2) return; // a row per wave at most: keep every wave busy
+    }
+    e->deg_window = W;
+    e->deg_quant = q;
+    e->row_group = (int)S;
+}
+
 int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     HIP_CHECK(hipSetDevice(e->device));
     if (e->d_xadj) free_graph_state(e); // re-load on a live engine
@@ -1593,7 +1660,24 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     e->d_sigma_inv.reserve(lnv);
     const int32_t *hint = mv_graph_locality_hint(g);
     e->has_hint = hint != nullptr;
-    if (hint) {
+    // K4 geometry first: the windowed degree order depends on it
+    e->sweep_grid = grid_for(lnv, 256, 2048);
+    e->skewed = e->max_degree > 256;
+    choose_degree_windows(e);
+    if (hint && e->deg_window) {
+        // uniform-degree SELL slices: refine the hint inside its spatial
+        // windows (mv_degree_window_order). sigma carries it, so perm stays
+        // the identity and every per-vertex array stays coalesced.
+        std::vector<int32_t> refined(lnv);
+        if (mv_degree_window_order(hint, xadj, lnv, e->deg_window,
+                                   e->deg_quant, e->row_group,
+                                   refined.data()) != 0) {
+            std::fprintf(stderr, "mv_engine_load_graph: bad degree window\n");
+            return -1;
+        }
+        HIP_CHECK(hipMemcpy(e->d_sigma, refined.data(), 4 * lnv,
+                            hipMemcpyHostToDevice));
+    } else if (hint) {
         HIP_CHECK(hipMemcpy(e->d_sigma, hint, 4 * lnv, hipMemcpyHostToDevice));
     } else {
         k_iota32<<<grid_for(lnv), 256>>>(lnv, e->d_sigma);
@@ -1632,8 +1716,6 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     // SELL order is forced degree-descending and extents follow the
     // per-thread first-vertex degree (k_spill_need), so the total stays
     // O(lne) instead of O(threads * max_degree).
-    e->sweep_grid = grid_for(lnv, 256, 2048);
-    e->skewed = e->max_degree > 256;
     const i64 nthreads = (i64)e->sweep_grid * 256;
     e->d_spill_off.reserve(nthreads);
 
@@ -1668,6 +1750,10 @@ void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out) {
     out->rows_sorted = e->rows_sorted;
     out->sell_sorted = e->sell_sorted;
     out->unit_weights = e->unit_weights;
+    out->deg_window = e->deg_window;
+    out->deg_quant = e->deg_quant;
+    out->row_group = e->row_group;
+    out->sell_entries = e->sell_entries;
 }
 
 void mv_engine_get_halo_info(const mv_engine *e, mv_halo_info *out) {
@@ -1993,6 +2079,7 @@ static void build_sell(mv_engine *e) {
         HIP_CHECK(hipMemcpyAsync(&total, e->d_chunk_off + e->nchunks, 8,
                                  hipMemcpyDeviceToHost, st));
         HIP_CHECK(hipStreamSynchronize(st));
+        e->sell_entries = total;
         e->d_sell_tidx.reserve(total);
         if (!e->unit_weights) e->d_sell_w.reserve(total);
         k_fill_sell<<<grid_for(lnv), 256, 0, st>>>(
@@ -2522,7 +2609,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
             e->sweep.general_slots[mv_sweep_slot_index(S)]++;
             k4_sweep<decltype(mr_tag)::value, S, decltype(unit_tag)::value>
                 <<<range_grid(s0, s1), 256, S * 256 * 12, st>>>(
-                    s0, s1, lnv, e->base, e->d_perm, e->d_deg,
+                    s0, s1, e->row_group, lnv, e->base, e->d_perm, e->d_deg,
                     e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, vcurr,
                     e->d_vghost, e->d_vdeg, e->d_sigma, e->d_cinfo,
                     e->d_cupd, e->d_rc_ids, e->d_rc_info, e->d_rcu,
@@ -2552,7 +2639,7 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
             k4_sweep_iter1<decltype(mr_tag)::value, decltype(unit_tag)::value,
                            decltype(lblasc_tag)::value>
                 <<<range_grid(s0, s1), 256, 0, st>>>(
-                    s0, s1, lnv, e->base, e->d_perm, e->d_deg,
+                    s0, s1, e->row_group, lnv, e->base, e->d_perm, e->d_deg,
                     e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, e->d_vghost,
                     e->d_ghosts, e->d_vdeg, e->d_sigma, e->d_cupd,
                     e->d_rc_info, e->d_rcu, constant, vtarget, e->d_cw);

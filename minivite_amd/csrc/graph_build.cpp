@@ -535,4 +535,50 @@ const int32_t *mv_graph_locality_hint(const mv_graph *g) {
     return g->locality_perm.empty() ? nullptr : g->locality_perm.data();
 }
 
+// Windowed degree order (header: mv_degree_window_order). Each window is
+// sorted on its own, so the windows run in parallel; std::stable_sort keeps
+// hint order among equal keys, which keeps equal-degree neighbours in space
+// neighbours in memory.
+int mv_degree_window_order(const int32_t *hint, const int64_t *xadj,
+                           int64_t lnv, int64_t window, int64_t quant,
+                           int64_t group, int32_t *out) {
+    auto pow2 = [](int64_t x) { return x > 0 && (x & (x - 1)) == 0; };
+    if (lnv < 0 || !xadj || !out || !pow2(window) || window < 128 ||
+        quant < 1 || !pow2(group) || group > window / 64)
+        return 1;
+    const int64_t nwin = (lnv + window - 1) / window;
+    const int64_t R = window / 64, G = R / group;
+#pragma omp parallel
+    {
+        std::vector<int64_t> key(window);
+        std::vector<int32_t> idx(window), sorted(window);
+#pragma omp for schedule(static)
+        for (int64_t wi = 0; wi < nwin; wi++) {
+            const int64_t b = wi * window;
+            const int64_t n = std::min(window, lnv - b);
+            for (int64_t k = 0; k < n; k++) {
+                const int64_t v = hint ? hint[b + k] : b + k;
+                key[k] = (xadj[v + 1] - xadj[v] + quant - 1) / quant;
+                idx[k] = (int32_t)k;
+            }
+            std::stable_sort(idx.begin(), idx.begin() + n,
+                             [&](int32_t a, int32_t c) {
+                                 return key[a] > key[c];
+                             });
+            for (int64_t k = 0; k < n; k++)
+                sorted[k] = hint ? hint[b + idx[k]] : (int32_t)(b + idx[k]);
+            if (n < window || G == 1) { // short last window / plain order
+                std::copy(sorted.begin(), sorted.begin() + n, out + b);
+                continue;
+            }
+            for (int64_t r = 0; r < R; r++) {
+                const int64_t pos = (r % G) * group + r / G;
+                std::copy(sorted.begin() + r * 64,
+                          sorted.begin() + r * 64 + 64, out + b + pos * 64);
+            }
+        }
+    }
+    return 0;
+}
+
 } // extern "C"
