@@ -205,6 +205,36 @@ typedef struct {
     int64_t row_group;        /* rows of 64 positions a wave takes in turn
                                * in k4_sweep / k4_sweep_iter1 */
     int64_t sell_entries;     /* SELL image entries, padding included */
+    /* Row queue of k4_sweep, decided at graph load. MV_SWEEP_UNIT (rows
+     * per unit, 0 = off) and MV_SWEEP_GRID (caps the grid of k4_sweep and
+     * k4_sweep_iter1, in blocks; the spill extents follow it; unset or 0 =
+     * no cap) are read at every load. With sched_unit = U > 0 the rows of
+     * a queued launch are cut into units of U rows; every wave starts with
+     * the unit of its own index and takes the remaining ones from per-block-
+     * group ticket words, one returning atomic add per unit plus one that
+     * finds its queue dry, and the launch's grid is held to one resident
+     * round (the occupancy query); row_group then only describes the
+     * layout. Without MV_SWEEP_UNIT, U is the largest of 4 and 2 that
+     * leaves every wave of the full grid two units or more, else 0;
+     * a unit set through MV_SWEEP_UNIT is honoured as given. Either way
+     * only the launches after the first-iterations slot variant queue
+     * (MV_FIRST_ITERS), unless MV_SWEEP_QUEUE_FROM (read at load) names
+     * another first iteration. k4_sweep_iter1, skewed graphs
+     * (their spill extents are sized for the static schedule; they report
+     * 0) and everything else keep the static row-group schedule. The
+     * ticket words are zeroed at load and never reset: sched_tickets is
+     * their sum when this call is made (with sched_unit > 0 the call waits
+     * for the engine's stream and copies them; otherwise it touches no
+     * device state), sched_tickets_expected the host's running total, over every
+     * queued launch since the load, of one ticket per unit. The two are
+     * equal exactly when every launch drained its queues and no wave
+     * pulled past its first dry ticket. */
+    int64_t sched_unit;       /* effective U (0 = static schedule) */
+    int64_t sched_grid;       /* blocks of the last k4_sweep launch that ran
+                               * to the end of the vertex range (the full
+                               * range unless the halo overlap splits it) */
+    int64_t sched_tickets;
+    int64_t sched_tickets_expected;
 } mv_sweep_info;
 void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
 

@@ -51,6 +51,10 @@ class MvSweepInfo(ctypes.Structure):
         ("deg_quant", ctypes.c_int64),
         ("row_group", ctypes.c_int64),
         ("sell_entries", ctypes.c_int64),
+        ("sched_unit", ctypes.c_int64),
+        ("sched_grid", ctypes.c_int64),
+        ("sched_tickets", ctypes.c_int64),
+        ("sched_tickets_expected", ctypes.c_int64),
     ]
 
 
@@ -523,7 +527,10 @@ class Engine:
 
     def sweep_info(self):
         """Kernel shapes launched by the last run() and the routing state
-        behind them (mv_sweep_info); general_slots becomes {SLOTS: count}."""
+        behind them (mv_sweep_info); general_slots becomes {SLOTS: count}.
+        With the row queue on (sched_unit > 0) the call waits for the
+        engine's stream and copies the eight ticket words from the device;
+        otherwise it touches only host state."""
         s = MvSweepInfo()
         lib().mv_engine_get_sweep_info(self.h, ctypes.byref(s))
         d = {f: getattr(s, f) for f, _ in s._fields_}

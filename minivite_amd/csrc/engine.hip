@@ -491,6 +491,17 @@ __global__ void k_apply_deltas(i64 n, const i64 *__restrict__ ids, i64 base,
     }
 }
 
+// A localCupdate entry nobody moved into or out of is still the all-zero
+// bits K6 left there: applying it changes nothing (x + 0 == x, and a sum of
+// non-negative degrees is never -0.0) and re-zeroing it rewrites what is there,
+// so K6/K67 skip both stores. After the first few iterations that is ~98%
+// of the entries, i.e. 32 B/vertex of write traffic per iteration. The test
+// is on BITS: a -0.0 degree (deltas that cancelled) is not "clear" and
+// takes the full path, so no sign can be left behind.
+__device__ __forceinline__ bool cupd_is_clear(const Cinfo &u) {
+    return (u.size | __double_as_longlong(u.degree)) == 0;
+}
+
 // ---- K6: apply localCupdate (dspl.hpp:458-471), fused with the next
 // iteration's K5 zeroing of localCupdate (dspl.hpp:483-484) ----
 __global__ void k6_apply_local(i64 lnv, Cinfo *__restrict__ cupd,
@@ -498,6 +509,7 @@ __global__ void k6_apply_local(i64 lnv, Cinfo *__restrict__ cupd,
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < lnv;
          i += (i64)gridDim.x * blockDim.x) {
         const Cinfo u = cupd[i];
+        if (cupd_is_clear(u)) continue; // nothing to apply, nothing to zero
         cinfo[i].size += u.size;
         cinfo[i].degree += u.degree;
         cupd[i] = {0, 0.0};
@@ -517,8 +529,10 @@ __global__ void k67_apply_and_partials(i64 lnv, Cinfo *__restrict__ cupd,
         const Cinfo u = cupd[i];
         const i64 nsz = cinfo[i].size + u.size;
         const double nde = cinfo[i].degree + u.degree;
-        cinfo[i] = {nsz, nde};
-        cupd[i] = {0, 0.0};
+        if (!cupd_is_clear(u)) {
+            cinfo[i] = {nsz, nde};
+            cupd[i] = {0, 0.0};
+        }
         a += cw[i];
         b += nde * nde;
     }
@@ -777,28 +791,106 @@ __device__ __forceinline__ void wave_reduce_best(double &bg, i64 &bl,
 }
 
 // Row schedule of the lane-per-vertex sweeps (k4_sweep, k4_sweep_iter1).
-// Row r of a launch is positions s_begin + 64r .. + 63, one per lane. Wave
-// x takes rows xS .. xS+S-1 in order, then advances by (waves of the
-// launch) * S rows: with the windowed degree order every wave then walks
-// whole groups of S rows, each a sample of its window's degree spectrum,
-// instead of the same degree rank of every window (a grid stride of 8192
-// waves is a multiple of every window length). S == 1 is the plain grid
-// stride. Everything but s is wave-uniform. row_first: the lane's first
-// position; row_next: the step after a row, r counting the rows done in
-// the current group.
-__device__ __forceinline__ i64 row_first(i64 s_begin, i64 gthread, int S) {
-    return s_begin + (gthread >> 6) * 64 * S + (gthread & 63);
+// Row r of a launch is positions s_begin + 64r .. + 63, one per lane. The
+// rows are cut into consecutive units of U rows, unit k = rows [kU,
+// min((k+1)U, rows)); a wave walks the rows of a unit in order and then
+// gets its next unit in one of two ways. Everything but the lane's
+// position is wave-uniform (SGPRs).
+//
+// Static (RowQueue::ticket == nullptr): U is the row group S and wave x
+// takes units x, x + waves, x + 2*waves, ... With the windowed degree
+// order every wave then walks whole groups of S rows, each a sample of its
+// window's degree spectrum, instead of the same degree rank of every
+// window (a grid stride of 8192 waves is a multiple of every window
+// length). S == 1 is the plain grid stride.
+//
+// Queue (ticket != nullptr; non-skewed graphs only, see choose_row_queue).
+// Wave x still starts with unit x, but then takes units instead of owning a
+// fixed set. The units from `waves` on are dealt round-robin onto `heads`
+// ticket words, a word per group of blocks (block & (heads - 1): with the
+// round-robin block dispatch that is one word per XCD, but nothing depends
+// on it). Lane 0 does one returning device-scope atomicAdd on its block's
+// word, readfirstlane broadcasts it, and ticket i of head h is queued unit
+// i * heads + h. A wave stops at its first unit past the end, so a launch
+// over nu units consumes exactly nu tickets whatever the residency or the
+// arrival order — its queued units plus one dry ticket for each wave that
+// had a first unit — and each head a share the host knows in advance. No
+// barrier, no spin: a wave that starts late finds fewer units, and waves
+// that finish light units early take more of them. The words are never
+// reset; the host passes each launch the running totals as bases (launches
+// of one engine are serial on one stream). A launch takes far fewer than
+// 2^32 tickets, so the low words' difference is enough. Any thread may
+// then run any vertex, which is why the spill extents must be uniform
+// (k_spill_uniform) for this mode.
+// Why this shape (measured at n=2^22, experiments/RESULTS.md): one word
+// saturates near 88 returning adds/us, and a 0.24 ms launch with a ticket
+// per unit AND per first unit needs 130/us at U=2; even the one dry ticket
+// per wave, all landing as a round of waves ends, holds SIMD slots for
+// tens of microseconds on one word. Eight words and a ticket-free first
+// unit bring the queue's cost under what the even finish gains.
+constexpr int QUEUE_HEADS = 8;        // ticket words (one per XCD)
+constexpr int QUEUE_HEAD_STRIDE = 16; // u64 between them: a 128-B line each
+struct RowQueue {
+    unsigned long long *ticket; // device words, monotonic; null = static
+    unsigned base[QUEUE_HEADS]; // low word of each at launch start
+    int unit;                   // rows per unit (static: the row group S)
+    int heads;                  // words in use: a power of two <= blocks
+};
+struct RowWalk {
+    int row;     // the current row of the launch
+    int row_end; // one past the current unit's last row
+    unsigned k;  // static: the current unit
+};
+// enter unit k of `unit` rows; returns the lane's first position, or s_end
+// past the end
+__device__ __forceinline__ i64 unit_enter(unsigned k, i64 s_begin, i64 s_end,
+                                          int unit, RowWalk &w) {
+    const i64 rows = (s_end - s_begin + 63) >> 6;
+    const i64 row = (i64)k * unit;
+    if (row >= rows) return s_end;
+    w.k = k;
+    w.row = (int)row;
+    w.row_end = (int)(row + unit < rows ? row + unit : rows);
+    return s_begin + row * 64 + (threadIdx.x & 63);
 }
-__device__ __forceinline__ i64 row_next(i64 s, int &r, int S, i64 stride) {
-    if (++r < S) return s + 64;
-    r = 0;
-    return s + 64 + (stride - 64) * S;
+// the next queued unit of this block's head h: its i-th ticket is queued
+// unit i * heads + h
+__device__ __forceinline__ unsigned queue_take(const RowQueue &q) {
+    const unsigned h = blockIdx.x & (q.heads - 1);
+    unsigned long long t = 0;
+    if ((threadIdx.x & 63) == 0)
+        t = atomicAdd(q.ticket + h * QUEUE_HEAD_STRIDE, 1ull);
+    const unsigned i =
+        __builtin_amdgcn_readfirstlane((unsigned)t) - q.base[h];
+    return i * q.heads + h;
+}
+__device__ __forceinline__ i64 row_first(i64 s_begin, i64 s_end, int unit,
+                                         RowWalk &w) {
+    const unsigned wave = __builtin_amdgcn_readfirstlane(
+        blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+    return unit_enter(wave, s_begin, s_end, unit, w);
+}
+// the step after a row: the static schedule alone (k4_sweep_iter1, which
+// never queues) ...
+__device__ __forceinline__ i64 row_next(i64 s, i64 s_begin, i64 s_end,
+                                        int unit, RowWalk &w) {
+    if (++w.row < w.row_end) return s + 64;
+    const unsigned waves = gridDim.x * (blockDim.x >> 6);
+    return unit_enter(waves + w.k, s_begin, s_end, unit, w);
+}
+// ... and k4_sweep's, static or queued by the launch
+__device__ __forceinline__ i64 row_next(i64 s, i64 s_begin, i64 s_end,
+                                        const RowQueue &q, RowWalk &w) {
+    if (++w.row < w.row_end) return s + 64;
+    const unsigned waves = gridDim.x * (blockDim.x >> 6);
+    return unit_enter(waves + (q.ticket ? queue_take(q) : w.k), s_begin,
+                      s_end, q.unit, w);
 }
 
 // ---- K4 general sweep: LDS slots + spill, any iteration ----
 template <bool MR, int SLOTS, bool UNIT>
 __global__ __launch_bounds__(256) void k4_sweep(
-    i64 s_begin, i64 s_end, int S_rows, i64 lnv, i64 base,
+    i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
     const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
@@ -809,20 +901,20 @@ __global__ __launch_bounds__(256) void k4_sweep(
     const Info16 *__restrict__ rc_info, Info16 *__restrict__ rcu,
     double constant, unsigned *__restrict__ vtarget,
     double *__restrict__ clusterWeight, unsigned *__restrict__ spill_keys,
-    double *__restrict__ spill_acc, const i64 *__restrict__ spill_off) {
+    double *__restrict__ spill_acc, const i64 *__restrict__ spill_off,
+    RowQueue queue) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     double *sacc = reinterpret_cast<double *>(smem);
     unsigned *skey = reinterpret_cast<unsigned *>(
         smem + sizeof(double) * SLOTS * blockDim.x);
     const int tid = threadIdx.x;
     const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
     unsigned *myspill_k = spill_keys + spill_off[gthread];
     double *myspill_a = spill_acc + spill_off[gthread];
 
-    int rdone = 0;
-    for (i64 s = row_first(s_begin, gthread, S_rows); s < s_end;
-         s = row_next(s, rdone, S_rows, stride)) {
+    RowWalk walk;
+    for (i64 s = row_first(s_begin, s_end, queue.unit, walk); s < s_end;
+         s = row_next(s, s_begin, s_end, queue, walk)) {
         const i64 i = perm[s];          // internal vertex index
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
@@ -1128,7 +1220,7 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
 // INTERNAL order instead and ties compare the batched labels explicitly.
 template <bool MR, bool UNIT, bool LBL_ASC>
 __global__ __launch_bounds__(256) void k4_sweep_iter1(
-    i64 s_begin, i64 s_end, int S_rows, i64 lnv, i64 base,
+    i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
     const int *__restrict__ sell_tidx, const double *__restrict__ sell_w,
@@ -1137,13 +1229,11 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1(
     Cinfo *__restrict__ cupd,
     const Info16 *__restrict__ rc_info, Info16 *__restrict__ rcu,
     double constant, unsigned *__restrict__ vtarget,
-    double *__restrict__ clusterWeight) {
+    double *__restrict__ clusterWeight, int S_rows) {
     using label = label_t<MR>;
-    const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
-    const i64 stride = (i64)gridDim.x * blockDim.x;
-    int rdone = 0;
-    for (i64 s = row_first(s_begin, gthread, S_rows); s < s_end;
-         s = row_next(s, rdone, S_rows, stride)) {
+    RowWalk walk;
+    for (i64 s = row_first(s_begin, s_end, S_rows, walk); s < s_end;
+         s = row_next(s, s_begin, s_end, S_rows, walk)) {
         const i64 i = perm[s];
         const int deg = (int)deg_int[i];
         const i64 ebase = chunk_off[s >> 6] + (s & 63);
@@ -1413,6 +1503,17 @@ struct mv_graph_state {
     int skewed = 0;
     int sweep_grid = 0;
 
+    // row queue of the lane-per-vertex sweeps (RowQueue): rows per unit
+    // (0 = static schedule), the ticket word (zeroed at load, never reset)
+    // and the host's running total of tickets its launches must consume
+    int sched_unit = 0;
+    int sched_from = 0; // first iteration whose k4_sweep launches queue
+                        // (MV_SWEEP_QUEUE_FROM; 0 = after the first-
+                        // iterations slot variant)
+    int sched_grid = 0; // blocks of the last k4_sweep launch that ran to lnv
+    DevBuf<unsigned long long> d_ticket; // QUEUE_HEADS strided words
+    unsigned long long tickets_total[QUEUE_HEADS] = {};
+
     // hash-aggregation bands over the degree-sorted positions:
     // [0, nhi) = wave-per-vertex hubs (unit only), [nhi, nlh) = lane-hash
     // band, [nlh, lnv) = LDS slots + linear spill
@@ -1442,6 +1543,10 @@ struct mv_graph_state {
 
 struct mv_engine : mv_graph_state {
     int device = 0, rank = 0, nranks = 1;
+    int num_cus = 1; // compute units of the device
+    // resident blocks per CU of this engine's k4_sweep instantiations, by
+    // [SLOTS index][UNIT] (the occupancy query; 0 = not asked yet)
+    int sweep_per_cu[7][2] = {};
     ncclComm_t comm = nullptr;
     ncclComm_t comm2 = nullptr; // halo #1a's communicator (overlap mode)
     mv_lb_session *lb = nullptr;
@@ -1495,6 +1600,9 @@ static mv_engine *engine_new(const char *who, int device, int rank,
     e->rank = rank;
     e->nranks = nranks;
     HIP_CHECK(hipSetDevice(device));
+    HIP_CHECK(hipDeviceGetAttribute(&e->num_cus,
+                                    hipDeviceAttributeMultiprocessorCount,
+                                    device));
     HIP_CHECK(hipStreamCreate(&e->stream));
     HIP_CHECK(hipStreamCreate(&e->stream2));
     HIP_CHECK(hipEventCreate(&e->ev_p1));
@@ -1604,6 +1712,47 @@ static void choose_degree_windows(mv_engine *e) {
     e->row_group = (int)S;
 }
 
+// Largest default queue unit (rows) of the general sweep: the best cell of
+// the measured U x grid table (experiments/RESULTS.md, "row queue").
+constexpr int SWEEP_UNIT_DEFAULT = 4;
+
+// Decide the row queue of this graph's general sweeps and the grid cap
+// (mv_sweep_info documents both). Runs after choose_degree_windows, which
+// keeps seeing the uncapped grid: the layout rule does not depend on these
+// knobs. MV_SWEEP_UNIT / MV_SWEEP_GRID / MV_SWEEP_QUEUE_FROM are read at
+// every load (perf only, results identical).
+static void choose_row_queue(mv_engine *e) {
+    const char *us = getenv("MV_SWEEP_UNIT");
+    const char *gs = getenv("MV_SWEEP_GRID");
+    const int cap = gs ? atoi(gs) : 0;
+    if (cap > 0) e->sweep_grid = std::min(e->sweep_grid, cap);
+    int U = 0;
+    if (us) { // an explicit unit is honoured even where waves then idle
+        U = atoi(us);
+        if (U < 0 || U > 4096) {
+            std::fprintf(stderr, "MV_SWEEP_UNIT must be in [0, 4096]: "
+                                 "static row schedule\n");
+            U = 0;
+        }
+    } else { // at least two units per wave, or the queue has nothing to do
+        const i64 rows = (e->lnv + 63) / 64;
+        const i64 per_wave = rows / (4 * (i64)e->sweep_grid);
+        for (U = SWEEP_UNIT_DEFAULT; U > 2 && 2 * U > per_wave; U /= 2) {}
+        if (2 * U > per_wave) U = 0;
+    }
+    // skewed graphs size each thread's spill from the vertices the static
+    // schedule hands it (k_spill_need): only uniform extents let any
+    // thread take any vertex
+    e->sched_unit = e->skewed ? 0 : U;
+    const char *fs = getenv("MV_SWEEP_QUEUE_FROM");
+    e->sched_from = fs ? std::max(atoi(fs), 0) : 0;
+    e->sched_grid = 0;
+    for (auto &t : e->tickets_total) t = 0;
+    e->d_ticket.reserve(QUEUE_HEADS * QUEUE_HEAD_STRIDE);
+    HIP_CHECK(hipMemset(e->d_ticket, 0,
+                        8 * QUEUE_HEADS * QUEUE_HEAD_STRIDE));
+}
+
 int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     HIP_CHECK(hipSetDevice(e->device));
     if (e->d_xadj) free_graph_state(e); // re-load on a live engine
@@ -1664,6 +1813,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     e->sweep_grid = grid_for(lnv, 256, 2048);
     e->skewed = e->max_degree > 256;
     choose_degree_windows(e);
+    choose_row_queue(e);
     if (hint && e->deg_window) {
         // uniform-degree SELL slices: refine the hint inside its spatial
         // windows (mv_degree_window_order). sigma carries it, so perm stays
@@ -1754,6 +1904,21 @@ void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out) {
     out->deg_quant = e->deg_quant;
     out->row_group = e->row_group;
     out->sell_entries = e->sell_entries;
+    out->sched_unit = e->sched_unit;
+    out->sched_grid = e->sched_grid;
+    out->sched_tickets_expected = 0;
+    for (auto t : e->tickets_total) out->sched_tickets_expected += (int64_t)t;
+    out->sched_tickets = 0;
+    // the device words, read now (after the run's work): the one part of
+    // this call that touches the device, and only with the queue on
+    if (e->sched_unit && e->d_ticket) {
+        unsigned long long t[QUEUE_HEADS];
+        HIP_CHECK(hipSetDevice(e->device));
+        HIP_CHECK(hipStreamSynchronize(e->stream));
+        HIP_CHECK(hipMemcpy2D(t, 8, e->d_ticket, 8 * QUEUE_HEAD_STRIDE, 8,
+                              QUEUE_HEADS, hipMemcpyDeviceToHost));
+        for (auto v : t) out->sched_tickets += (int64_t)v;
+    }
 }
 
 void mv_engine_get_halo_info(const mv_engine *e, mv_halo_info *out) {
@@ -2600,22 +2765,70 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         const unsigned *vcurr = p == 1 ? (const unsigned *)d_curr : e->d_vcurr;
         unsigned *vtarget = p == 1 ? (unsigned *)d_target : e->d_vtarget;
         auto range_grid = [&](i64 s0, i64 s1) {
-            return p == 1 ? e->sweep_grid : grid_for(s1 - s0, 256, 2048);
+            return p == 1 ? e->sweep_grid
+                          : grid_for(s1 - s0, 256, e->sweep_grid);
+        };
+        // Row schedule of a lane-per-vertex launch. By default the queue
+        // serves the general sweep from iteration first_iters + 1 on: in
+        // the first iterations nearly every vertex moves, the tickets then
+        // wait behind the moves' own cupd atomics and the queue loses
+        // (measured, experiments/RESULTS.md). MV_SWEEP_QUEUE_FROM moves
+        // that first iteration (tests reach the queue on graphs that
+        // converge in two). k4_sweep_iter1 and the launches that do not
+        // queue keep the static schedule and the full grid.
+        const RowQueue static_rows{nullptr, {}, e->row_group, 0};
+        const bool queued =
+            e->sched_unit > 0 &&
+            numIters >= (e->sched_from ? e->sched_from : first_iters + 1);
+        // the queue's launch view; the host totals advance by the tickets
+        // the launch will consume, nu in all (see RowQueue)
+        auto take_queue = [&](i64 s0, i64 s1, int grid) {
+            RowQueue q{e->d_ticket, {}, e->sched_unit, 1};
+            while (q.heads * 2 <= std::min(grid, QUEUE_HEADS)) q.heads *= 2;
+            const i64 H = q.heads;
+            const i64 rows = (s1 - s0 + 63) / 64;
+            const i64 nu = (rows + q.unit - 1) / q.unit, nw = 4 * (i64)grid;
+            const i64 nq = std::max<i64>(nu - nw, 0); // queued units
+            const i64 m = std::min(nu, nw); // waves with a first unit: each
+                                            // ends on one dry ticket
+            auto share = [H](i64 n, i64 h) { // |{j < n : j % H == h}|
+                return n > h ? (n - h + H - 1) / H : 0;
+            };
+            for (i64 h = 0; h < H; h++) {
+                q.base[h] = (unsigned)e->tickets_total[h];
+                e->tickets_total[h] += share(nq, h) + 4 * share(m / 4, h) +
+                                       ((m / 4) % H == h ? m % 4 : 0);
+            }
+            return q;
         };
         auto launch_sweep = [&](auto mr_tag, auto slots_tag, auto unit_tag,
                                 i64 s0, i64 s1) {
             constexpr int S = decltype(slots_tag)::value; // 12 B/lane LDS
+            const auto kernel = k4_sweep<decltype(mr_tag)::value, S,
+                                         decltype(unit_tag)::value>;
             e->sweep.general++;
             e->sweep.general_slots[mv_sweep_slot_index(S)]++;
-            k4_sweep<decltype(mr_tag)::value, S, decltype(unit_tag)::value>
-                <<<range_grid(s0, s1), 256, S * 256 * 12, st>>>(
-                    s0, s1, e->row_group, lnv, e->base, e->d_perm, e->d_deg,
-                    e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, vcurr,
-                    e->d_vghost, e->d_vdeg, e->d_sigma, e->d_cinfo,
-                    e->d_cupd, e->d_rc_ids, e->d_rc_info, e->d_rcu,
-                    constant, vtarget, e->d_cw,
-                    (unsigned *)e->d_spill_k.get(), e->d_spill_a,
-                    e->d_spill_off);
+            int grid = range_grid(s0, s1);
+            if (queued) {
+                // one resident round: a first unit on a block that starts
+                // late is a unit no other wave can take
+                int &per_cu = e->sweep_per_cu[mv_sweep_slot_index(S)]
+                                             [decltype(unit_tag)::value];
+                if (!per_cu) { // once per engine and instantiation
+                    HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
+                        &per_cu, kernel, 256, S * 256 * 12));
+                    per_cu = std::max(per_cu, 1);
+                }
+                grid = std::min(grid, per_cu * e->num_cus);
+            }
+            if (s1 == lnv) e->sched_grid = grid;
+            kernel<<<grid, 256, S * 256 * 12, st>>>(
+                s0, s1, lnv, e->base, e->d_perm, e->d_deg, e->d_chunk_off,
+                e->d_sell_tidx, e->d_sell_w, vcurr, e->d_vghost, e->d_vdeg,
+                e->d_sigma, e->d_cinfo, e->d_cupd, e->d_rc_ids, e->d_rc_info,
+                e->d_rcu, constant, vtarget, e->d_cw,
+                (unsigned *)e->d_spill_k.get(), e->d_spill_a, e->d_spill_off,
+                queued ? take_queue(s0, s1, grid) : static_rows);
         };
         auto dispatch_slots = [&](auto mr_tag, auto unit_tag, i64 s0,
                                   i64 s1) {
@@ -2639,10 +2852,11 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
             k4_sweep_iter1<decltype(mr_tag)::value, decltype(unit_tag)::value,
                            decltype(lblasc_tag)::value>
                 <<<range_grid(s0, s1), 256, 0, st>>>(
-                    s0, s1, e->row_group, lnv, e->base, e->d_perm, e->d_deg,
+                    s0, s1, lnv, e->base, e->d_perm, e->d_deg,
                     e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, e->d_vghost,
                     e->d_ghosts, e->d_vdeg, e->d_sigma, e->d_cupd,
-                    e->d_rc_info, e->d_rcu, constant, vtarget, e->d_cw);
+                    e->d_rc_info, e->d_rcu, constant, vtarget, e->d_cw,
+                    e->row_group);
         };
         if (e->nlh > 0) { // hash-aggregation bands (skewed graphs)
             HIP_CHECK(hipMemsetAsync(e->d_hkeys, 0xFF, 8 * e->hash_total,
