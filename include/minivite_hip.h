@@ -235,6 +235,11 @@ typedef struct {
                                * range unless the halo overlap splits it) */
     int64_t sched_tickets;
     int64_t sched_tickets_expected;
+    int64_t perm_identity;    /* 1: SELL position s holds internal vertex s
+                               * (locality hint, not skewed, no exports-first
+                               * partition), and the identity variants of
+                               * k4_sweep / k4_sweep_iter1, which never read
+                               * the permutation, are the ones launched */
 } mv_sweep_info;
 void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
 

@@ -55,6 +55,7 @@ class MvSweepInfo(ctypes.Structure):
         ("sched_grid", ctypes.c_int64),
         ("sched_tickets", ctypes.c_int64),
         ("sched_tickets_expected", ctypes.c_int64),
+        ("perm_identity", ctypes.c_int64),
     ]
 
 

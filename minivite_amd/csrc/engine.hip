@@ -685,17 +685,29 @@ __device__ __forceinline__ void move_update(unsigned from, unsigned to,
 // dspl.hpp:240-271). Steps past the row end re-load the row's first slot.
 constexpr int CH = 8;
 
-template <bool UNIT>
+template <bool UNIT, typename T>
 __device__ __forceinline__ void load_tails(i64 ebase, int k0, int m,
                                            const int *sell_tidx,
                                            const double *sell_w,
-                                           i64 (&tb)[CH], double (&wb)[CH]) {
+                                           T (&tb)[CH], double (&wb)[CH]) {
 #pragma unroll
     for (int j = 0; j < CH; j++) {
         const i64 slot = (j < m) ? ebase + (i64)(k0 + j) * 64 : ebase;
         tb[j] = sell_tidx[slot];
         if (!UNIT) wb[j] = sell_w[slot];
     }
+}
+
+// the communities of a chunk's tails
+template <bool MR, typename T>
+__device__ __forceinline__ void gather_comms(const T (&tb)[CH], i64 lnv,
+                                             const unsigned *vcurr,
+                                             const unsigned *vghost,
+                                             unsigned (&cb)[CH]) {
+#pragma unroll
+    for (int j = 0; j < CH; j++)
+        cb[j] = (!MR || tb[j] < lnv) ? vcurr[tb[j]]
+                                     : vghost[clamp0(tb[j] - lnv)];
 }
 
 // tails (+ weights unless UNIT) and their communities
@@ -708,10 +720,7 @@ __device__ __forceinline__ void load_chunk(i64 ebase, int k0, int m, i64 lnv,
                                            i64 (&tb)[CH], double (&wb)[CH],
                                            unsigned (&cb)[CH]) {
     load_tails<UNIT>(ebase, k0, m, sell_tidx, sell_w, tb, wb);
-#pragma unroll
-    for (int j = 0; j < CH; j++)
-        cb[j] = (!MR || tb[j] < lnv) ? vcurr[tb[j]]
-                                     : vghost[clamp0(tb[j] - lnv)];
+    gather_comms<MR>(tb, lnv, vcurr, vghost, cb);
 }
 
 // dQ gain (dspl.hpp:212) — operand order and parenthesisation are the
@@ -853,43 +862,80 @@ __device__ __forceinline__ i64 unit_enter(unsigned k, i64 s_begin, i64 s_end,
     w.row_end = (int)(row + unit < rows ? row + unit : rows);
     return s_begin + row * 64 + (threadIdx.x & 63);
 }
-// the next queued unit of this block's head h: its i-th ticket is queued
-// unit i * heads + h
-__device__ __forceinline__ unsigned queue_take(const RowQueue &q) {
-    const unsigned h = blockIdx.x & (q.heads - 1);
-    unsigned long long t = 0;
-    if ((threadIdx.x & 63) == 0)
-        t = atomicAdd(q.ticket + h * QUEUE_HEAD_STRIDE, 1ull);
-    const unsigned i =
-        __builtin_amdgcn_readfirstlane((unsigned)t) - q.base[h];
-    return i * q.heads + h;
+// Every lane-per-vertex launch has 256-thread blocks (__launch_bounds__ and
+// the launch sites), so the walk takes the block size as a constant: read
+// from the dispatch packet it is a vector load, and its wait at a unit end
+// also drains the row's stores and atomics (they count in vmcnt on gfx950).
+constexpr int SWEEP_BLOCK = 256;
+__device__ __forceinline__ unsigned sweep_waves() {
+    return gridDim.x * (SWEEP_BLOCK >> 6);
 }
 __device__ __forceinline__ i64 row_first(i64 s_begin, i64 s_end, int unit,
                                          RowWalk &w) {
     const unsigned wave = __builtin_amdgcn_readfirstlane(
-        blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6));
+        blockIdx.x * (SWEEP_BLOCK >> 6) + (threadIdx.x >> 6));
     return unit_enter(wave, s_begin, s_end, unit, w);
 }
-// the step after a row: the static schedule alone (k4_sweep_iter1, which
-// never queues) ...
+// the step after a row of the static schedule
 __device__ __forceinline__ i64 row_next(i64 s, i64 s_begin, i64 s_end,
-                                        int unit, RowWalk &w) {
+                                        int unit, unsigned waves, RowWalk &w) {
     if (++w.row < w.row_end) return s + 64;
-    const unsigned waves = gridDim.x * (blockDim.x >> 6);
     return unit_enter(waves + w.k, s_begin, s_end, unit, w);
 }
-// ... and k4_sweep's, static or queued by the launch
+// The queue's ticket is taken in two halves, so that its round trip is not
+// paid on its own at the unit's end. queue_request runs in the last row of a
+// unit, right after that row's first loads have been issued: lane 0 asks for
+// the next queued unit of this block's head h, and the wait for the answer
+// is the wait for those loads. row_next, after the row, turns the answer
+// into a unit: the i-th ticket of head h is queued unit i * heads + h. A
+// wave still takes exactly one ticket per unit it finishes. The answer is
+// wave-uniform and costs no VGPR.
+__device__ __forceinline__ unsigned queue_request(const RowQueue &q,
+                                                  const RowWalk &w) {
+    if (!q.ticket || w.row + 1 != w.row_end) return 0;
+    unsigned long long t = 0;
+    if ((threadIdx.x & 63) == 0)
+        t = atomicAdd(
+            q.ticket + (blockIdx.x & (q.heads - 1)) * QUEUE_HEAD_STRIDE,
+            1ull);
+    return __builtin_amdgcn_readfirstlane((unsigned)t);
+}
 __device__ __forceinline__ i64 row_next(i64 s, i64 s_begin, i64 s_end,
-                                        const RowQueue &q, RowWalk &w) {
+                                        const RowQueue &q, unsigned waves,
+                                        unsigned ticket, RowWalk &w) {
     if (++w.row < w.row_end) return s + 64;
-    const unsigned waves = gridDim.x * (blockDim.x >> 6);
-    return unit_enter(waves + (q.ticket ? queue_take(q) : w.k), s_begin,
-                      s_end, q.unit, w);
+    unsigned k = w.k;
+    if (q.ticket) {
+        const unsigned h = blockIdx.x & (q.heads - 1);
+        k = (ticket - q.base[h]) * q.heads + h;
+    }
+    return unit_enter(waves + k, s_begin, s_end, q.unit, w);
+}
+
+// A load that stays where it is written. The compiler sinks a plain load
+// into the branch that holds its only uses; for chunk_off that is the
+// deg != 0 side, one round trip later than the address was known. A relaxed
+// wavefront-scope atomic load is an ordinary global_load that is not moved.
+__device__ __forceinline__ i64 load_in_place(const i64 *p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WAVEFRONT);
 }
 
 // ---- K4 general sweep: LDS slots + spill, any iteration ----
-template <bool MR, int SLOTS, bool UNIT>
-__global__ __launch_bounds__(256) void k4_sweep(
+// IDP: perm is the identity (mv_graph_state::perm_identity), so a position
+// is its vertex and the row starts without the perm round trip.
+// The row's loads are ordered by when their values are needed, not by where
+// they are used: chunk_off (a function of the position alone) goes out with
+// perm; deg, vcurr and, for weighted graphs, vDegree in the next trip (a
+// unit graph's vDegree is (double)deg, K1), and with them the queue's
+// ticket; cinfo[cc], which only the gain scan reads, with the first tail
+// loads, so that it travels under the edge loop. The tails stay guarded by
+// deg: the SELL padding is never written and
+// a trailing slice of isolated vertices has width 0.
+template <bool MR, int SLOTS, bool UNIT, bool IDP>
+__global__ __launch_bounds__(SWEEP_BLOCK)
+__attribute__((amdgpu_waves_per_eu(UNIT ? 6 : 5)))
+void k4_sweep(
     i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
@@ -904,36 +950,43 @@ __global__ __launch_bounds__(256) void k4_sweep(
     double *__restrict__ spill_acc, const i64 *__restrict__ spill_off,
     RowQueue queue) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
+    constexpr int B = SWEEP_BLOCK;
     double *sacc = reinterpret_cast<double *>(smem);
-    unsigned *skey = reinterpret_cast<unsigned *>(
-        smem + sizeof(double) * SLOTS * blockDim.x);
+    unsigned *skey =
+        reinterpret_cast<unsigned *>(smem + sizeof(double) * SLOTS * B);
     const int tid = threadIdx.x;
-    const i64 gthread = blockIdx.x * (i64)blockDim.x + threadIdx.x;
+    const i64 gthread = blockIdx.x * (i64)B + threadIdx.x;
     unsigned *myspill_k = spill_keys + spill_off[gthread];
     double *myspill_a = spill_acc + spill_off[gthread];
+    const unsigned waves = sweep_waves();
 
     RowWalk walk;
-    for (i64 s = row_first(s_begin, s_end, queue.unit, walk); s < s_end;
-         s = row_next(s, s_begin, s_end, queue, walk)) {
-        const i64 i = perm[s];          // internal vertex index
+    for (i64 s = row_first(s_begin, s_end, queue.unit, walk); s < s_end;) {
+        const i64 coff = load_in_place(chunk_off + (s >> 6));
+        const i64 i = IDP ? (unsigned)s : perm[s]; // internal vertex index
+                                                   // (lnv < 2^32)
         const int deg = (int)deg_int[i];
-        const i64 ebase = chunk_off[s >> 6] + (s & 63);
         const unsigned cc = vcurr[i];
-        const Cinfo cci = comm_info<MR>(cc, lnv, cinfo, rc_info);
+        double vdeg = 0.0;
+        if (!UNIT) vdeg = vDegree[i];
+        const unsigned ticket = queue_request(queue, walk);
+        const i64 ebase = coff + (s & 63);
         unsigned target;
         if (deg == 0) {
             target = cc;          // dspl.hpp:323-324
             clusterWeight[i] = 0; // K5 semantics (dspl.hpp:481-482)
         } else {
+            if (UNIT) vdeg = (double)deg;
             double c0 = 0.0, selfLoop = 0.0;
             int ns = 0, nspill = 0;
-            for (int k0 = 0; k0 < deg; k0 += CH) {
-                const int m = min(CH, deg - k0);
-                i64 tb[CH];
+            int tb[CH];
+            double wb[CH];
+            int m = min(CH, deg);
+            load_tails<UNIT>(ebase, 0, m, sell_tidx, sell_w, tb, wb);
+            const Cinfo cci = comm_info<MR>(cc, lnv, cinfo, rc_info);
+            for (int k0 = 0;;) {
                 unsigned cb[CH];
-                double wb[CH];
-                load_chunk<MR, UNIT>(ebase, k0, m, lnv, sell_tidx, sell_w,
-                                     vcurr, vghost, tb, wb, cb);
+                gather_comms<MR>(tb, lnv, vcurr, vghost, cb);
                 for (int j = 0; j < m; j++) {
                     const i64 tidx = tb[j];
                     const double w = UNIT ? 1.0 : wb[j];
@@ -942,16 +995,16 @@ __global__ __launch_bounds__(256) void k4_sweep(
                     if (tcomm == cc) { c0 += w; continue; }
                     bool found = false;
                     for (int t = 0; t < ns; t++) {
-                        if (skey[t * blockDim.x + tid] == tcomm) {
-                            sacc[t * blockDim.x + tid] += w;
+                        if (skey[t * B + tid] == tcomm) {
+                            sacc[t * B + tid] += w;
                             found = true;
                             break;
                         }
                     }
                     if (found) continue;
                     if (ns < SLOTS) {
-                        skey[ns * blockDim.x + tid] = tcomm;
-                        sacc[ns * blockDim.x + tid] = w;
+                        skey[ns * B + tid] = tcomm;
+                        sacc[ns * B + tid] = w;
                         ns++;
                         continue;
                     }
@@ -968,34 +1021,38 @@ __global__ __launch_bounds__(256) void k4_sweep(
                         nspill++;
                     }
                 }
+                k0 += CH;
+                if (k0 >= deg) break;
+                m = min(CH, deg - k0);
+                load_tails<UNIT>(ebase, k0, m, sell_tidx, sell_w, tb, wb);
             }
             clusterWeight[i] = c0; // dspl.hpp:318 onto the K5-zeroed value
 
             // distGetMaxIndex: LDS slots first, then the spill in
-            // insertion order
-            const double vdeg = vDegree[i];
+            // insertion order — two loops, so that the slots are plain LDS
+            // reads (one loop selecting between the two address spaces
+            // compiles to flat loads waited for as vector memory)
             const double eix = c0 - selfLoop;
             const double ax = cci.degree - vdeg;
             double maxGain = 0.0;
             unsigned maxIndex = cc;
             i64 maxSize = cci.size;
-            const int tot = ns + nspill;
-            for (int t = 0; t < tot; t++) {
-                const unsigned y = (t < ns) ? skey[t * blockDim.x + tid]
-                                            : myspill_k[t - ns];
-                const double eiy = (t < ns) ? sacc[t * blockDim.x + tid]
-                                            : myspill_a[t - ns];
-                argmax_step<MR>(y, eiy, eix, vdeg, ax, constant, lnv, base,
-                                sigma, cinfo, rc_ids, rc_info, maxGain,
-                                maxIndex, maxSize);
-            }
+            for (int t = 0; t < ns; t++)
+                argmax_step<MR>(skey[t * B + tid], sacc[t * B + tid], eix,
+                                vdeg, ax, constant, lnv, base, sigma, cinfo,
+                                rc_ids, rc_info, maxGain, maxIndex, maxSize);
+            for (int t = 0; t < nspill; t++)
+                argmax_step<MR>(myspill_k[t], myspill_a[t], eix, vdeg, ax,
+                                constant, lnv, base, sigma, cinfo, rc_ids,
+                                rc_info, maxGain, maxIndex, maxSize);
             target = singleton_guard<MR>(maxIndex, maxSize, cc, cci.size, lnv,
                                          base, sigma, rc_ids);
         }
 
-        if (target != cc)
-            move_update<MR, MR>(cc, target, vDegree[i], lnv, cupd, rcu);
+        if (target != cc) // deg > 0 here, so vdeg is the vertex's
+            move_update<MR, MR>(cc, target, vdeg, lnv, cupd, rcu);
         vtarget[i] = target; // dspl.hpp:404 (view; persisted as a label)
+        s = row_next(s, s_begin, s_end, queue, waves, ticket, walk);
     }
 }
 
@@ -1218,8 +1275,9 @@ __global__ __launch_bounds__(256) void k4_sweep_lh(
 // strict-greater argmax implicitly keeps the smallest label on gain ties.
 // With internal-sorted rows (k_sell_sort_rows) candidates stream in
 // INTERNAL order instead and ties compare the batched labels explicitly.
-template <bool MR, bool UNIT, bool LBL_ASC>
-__global__ __launch_bounds__(256) void k4_sweep_iter1(
+// IDP and the order of the row's first loads: as in k4_sweep.
+template <bool MR, bool UNIT, bool LBL_ASC, bool IDP>
+__global__ __launch_bounds__(SWEEP_BLOCK) void k4_sweep_iter1(
     i64 s_begin, i64 s_end, i64 lnv, i64 base,
     const unsigned *__restrict__ perm,
     const unsigned *__restrict__ deg_int, const i64 *__restrict__ chunk_off,
@@ -1231,15 +1289,18 @@ __global__ __launch_bounds__(256) void k4_sweep_iter1(
     double constant, unsigned *__restrict__ vtarget,
     double *__restrict__ clusterWeight, int S_rows) {
     using label = label_t<MR>;
+    const unsigned waves = sweep_waves();
     RowWalk walk;
     for (i64 s = row_first(s_begin, s_end, S_rows, walk); s < s_end;
-         s = row_next(s, s_begin, s_end, S_rows, walk)) {
-        const i64 i = perm[s];
+         s = row_next(s, s_begin, s_end, S_rows, waves, walk)) {
+        const i64 coff = load_in_place(chunk_off + (s >> 6));
+        const i64 i = IDP ? (unsigned)s : perm[s]; // lnv < 2^32
         const int deg = (int)deg_int[i];
-        const i64 ebase = chunk_off[s >> 6] + (s & 63);
+        const i64 ebase = coff + (s & 63);
         const unsigned cc = (unsigned)i; // own slot (identity)
         const label ccLabel = own_label<MR>(i, base, sigma);
-        const double vdeg = vDegree[i];
+        // a unit graph's vDegree is the row length (K1)
+        const double vdeg = UNIT ? (double)deg : vDegree[i];
         double c0 = 0.0;
         double maxGain = 0.0;
         unsigned maxIndex = cc;
@@ -1426,6 +1487,7 @@ struct mv_graph_state {
     int unit_weights = 1;
     int rows_sorted = 1; // per-row tails ascending (reference CSR order)
     int sell_sorted = 0; // SELL rows re-sorted by internal index (unit)
+    int perm_identity = 0; // d_perm[s] == s: build_sell's iota, unpermuted
     i64 max_degree = 0;
 
     // internal layout
@@ -1545,8 +1607,8 @@ struct mv_engine : mv_graph_state {
     int device = 0, rank = 0, nranks = 1;
     int num_cus = 1; // compute units of the device
     // resident blocks per CU of this engine's k4_sweep instantiations, by
-    // [SLOTS index][UNIT] (the occupancy query; 0 = not asked yet)
-    int sweep_per_cu[7][2] = {};
+    // [SLOTS index][UNIT][IDP] (the occupancy query; 0 = not asked yet)
+    int sweep_per_cu[7][2][2] = {};
     ncclComm_t comm = nullptr;
     ncclComm_t comm2 = nullptr; // halo #1a's communicator (overlap mode)
     mv_lb_session *lb = nullptr;
@@ -1906,6 +1968,7 @@ void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out) {
     out->sell_entries = e->sell_entries;
     out->sched_unit = e->sched_unit;
     out->sched_grid = e->sched_grid;
+    out->perm_identity = e->perm_identity;
     out->sched_tickets_expected = 0;
     for (auto t : e->tickets_total) out->sched_tickets_expected += (int64_t)t;
     out->sched_tickets = 0;
@@ -2102,8 +2165,10 @@ static void build_sell(mv_engine *e) {
                                              e->d_deg);
     e->nhi = 0; // set by the skewed branch below when applicable
     e->nlh = 0;
+    e->perm_identity = 0;
     if (e->has_hint && !e->skewed) {
         k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm);
+        e->perm_identity = 1; // until something below permutes it
     } else {
         k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_iota);
         DevBuf<unsigned> d_degs; // temporaries: freed with this block
@@ -2223,6 +2288,7 @@ static void build_sell(mv_engine *e) {
                                  hipMemcpyDeviceToDevice, st));
         HIP_CHECK(hipStreamSynchronize(st));
         e->overlap = 1;
+        e->perm_identity = 0;
     }
 
     {
@@ -2802,10 +2868,11 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
             return q;
         };
         auto launch_sweep = [&](auto mr_tag, auto slots_tag, auto unit_tag,
-                                i64 s0, i64 s1) {
+                                auto idp_tag, i64 s0, i64 s1) {
             constexpr int S = decltype(slots_tag)::value; // 12 B/lane LDS
             const auto kernel = k4_sweep<decltype(mr_tag)::value, S,
-                                         decltype(unit_tag)::value>;
+                                         decltype(unit_tag)::value,
+                                         decltype(idp_tag)::value>;
             e->sweep.general++;
             e->sweep.general_slots[mv_sweep_slot_index(S)]++;
             int grid = range_grid(s0, s1);
@@ -2813,7 +2880,8 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                 // one resident round: a first unit on a block that starts
                 // late is a unit no other wave can take
                 int &per_cu = e->sweep_per_cu[mv_sweep_slot_index(S)]
-                                             [decltype(unit_tag)::value];
+                                             [decltype(unit_tag)::value]
+                                             [decltype(idp_tag)::value];
                 if (!per_cu) { // once per engine and instantiation
                     HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
                         &per_cu, kernel, 256, S * 256 * 12));
@@ -2833,7 +2901,10 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
         auto dispatch_slots = [&](auto mr_tag, auto unit_tag, i64 s0,
                                   i64 s1) {
             auto go = [&](auto slots_tag) {
-                launch_sweep(mr_tag, slots_tag, unit_tag, s0, s1);
+                by_flag(e->perm_identity, [&](auto idp_tag) {
+                    launch_sweep(mr_tag, slots_tag, unit_tag, idp_tag, s0,
+                                 s1);
+                });
             };
             switch (slots) {
             case 4: go(std::integral_constant<int, 4>{}); break;
@@ -2849,14 +2920,18 @@ double mv_engine_run(mv_engine *e, double lower, double thresh,
                                 i64 s0, i64 s1) {
             if (decltype(lblasc_tag)::value) e->sweep.iter1_label_order++;
             else e->sweep.iter1_internal_order++;
-            k4_sweep_iter1<decltype(mr_tag)::value, decltype(unit_tag)::value,
-                           decltype(lblasc_tag)::value>
-                <<<range_grid(s0, s1), 256, 0, st>>>(
-                    s0, s1, lnv, e->base, e->d_perm, e->d_deg,
-                    e->d_chunk_off, e->d_sell_tidx, e->d_sell_w, e->d_vghost,
-                    e->d_ghosts, e->d_vdeg, e->d_sigma, e->d_cupd,
-                    e->d_rc_info, e->d_rcu, constant, vtarget, e->d_cw,
-                    e->row_group);
+            by_flag(e->perm_identity, [&](auto idp_tag) {
+                k4_sweep_iter1<decltype(mr_tag)::value,
+                               decltype(unit_tag)::value,
+                               decltype(lblasc_tag)::value,
+                               decltype(idp_tag)::value>
+                    <<<range_grid(s0, s1), 256, 0, st>>>(
+                        s0, s1, lnv, e->base, e->d_perm, e->d_deg,
+                        e->d_chunk_off, e->d_sell_tidx, e->d_sell_w,
+                        e->d_vghost, e->d_ghosts, e->d_vdeg, e->d_sigma,
+                        e->d_cupd, e->d_rc_info, e->d_rcu, constant, vtarget,
+                        e->d_cw, e->row_group);
+            });
         };
         if (e->nlh > 0) { // hash-aggregation bands (skewed graphs)
             HIP_CHECK(hipMemsetAsync(e->d_hkeys, 0xFF, 8 * e->hash_total,
