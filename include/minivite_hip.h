@@ -100,6 +100,25 @@ int mv_degree_window_order(const int32_t *hint, const int64_t *xadj,
                            int64_t lnv, int64_t window, int64_t quant,
                            int64_t group, int32_t *out);
 
+/* The integer arithmetic of the sweep's row schedule (mv_sweep_info states
+ * the rules), as the engine computes it. Host only: needs no GPU and no
+ * engine. Three answers in one call:
+ *  - *default_unit: the queue unit U a graph of lnv vertices gets with no
+ *    MV_SWEEP_UNIT on a sweep grid of sweep_grid blocks (0 = static);
+ *  - *default_row_group: its row_group under the default degree window of
+ *    `window` vertices (0 = the windowed order is off for this graph);
+ *  - one queued launch over `positions` SELL positions in units of `unit`
+ *    rows on launch_grid blocks: the return value is the number of ticket
+ *    words in use, h (a power of two <= 8), and tickets[0..h) receive what
+ *    the launch takes from each word — one ticket per unit in all.
+ *    tickets has room for 8.
+ * Returns -1, writing nothing, for lnv, window or positions < 0 or
+ * sweep_grid, unit or launch_grid < 1. */
+int mv_sweep_schedule(int64_t lnv, int sweep_grid, int64_t window,
+                      int64_t positions, int unit, int launch_grid,
+                      int *default_unit, int64_t *default_row_group,
+                      int64_t *tickets);
+
 /* ---- the hot path (replaces distLouvainMethod, dspl.hpp:1280-1441) ---- */
 
 typedef struct mv_engine mv_engine;

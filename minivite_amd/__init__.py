@@ -11,6 +11,7 @@ from .api import (  # noqa: F401
     Hierarchy,
     coarsen_csr,
     degree_window_order,
+    sweep_schedule,
     LoopbackSession,
     comm_id,
     lib,

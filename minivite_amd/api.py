@@ -122,6 +122,11 @@ def lib():
         L.mv_degree_window_order.restype = ctypes.c_int
         L.mv_degree_window_order.argtypes = [pi32, pi64, i64, i64, i64, i64,
                                              pi32]
+        L.mv_sweep_schedule.restype = ctypes.c_int
+        L.mv_sweep_schedule.argtypes = [i64, ctypes.c_int, i64, i64,
+                                        ctypes.c_int, ctypes.c_int,
+                                        ctypes.POINTER(ctypes.c_int), pi64,
+                                        pi64]
         L.mv_comm_id.restype = ctypes.c_int
         L.mv_comm_id.argtypes = [ctypes.c_void_p]
         L.mv_lb_create.restype = vp
@@ -305,6 +310,21 @@ def degree_window_order(hint, xadj, window, quant=1, group=1):
         raise ValueError("window must be a power of two >= 128, quant >= 1, "
                          "group a power of two <= window/64")
     return out
+
+
+def sweep_schedule(lnv, sweep_grid, window=2048, positions=0, unit=1,
+                   launch_grid=1):
+    """mv_sweep_schedule on the host. Returns (default unit U, default
+    row_group, per-head ticket additions of one queued launch)."""
+    u = ctypes.c_int()
+    s = ctypes.c_int64()
+    tickets = np.zeros(8, dtype=np.int64)
+    heads = lib().mv_sweep_schedule(lnv, sweep_grid, window, positions, unit,
+                                    launch_grid, ctypes.byref(u),
+                                    ctypes.byref(s), _i64p(tickets))
+    if heads < 0:
+        raise ValueError("sizes must be >= 0, grids and unit >= 1")
+    return u.value, s.value, [int(t) for t in tickets[:heads]]
 
 
 def coarsen_csr(graph, comm, device=0):

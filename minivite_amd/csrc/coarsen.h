@@ -1,5 +1,6 @@
 // coarsen.h — internal seam between coarsen.hip (the community-aggregation
-// kernels) and engine.hip (the multi-phase driver). Not part of the C-ABI.
+// kernels) and multiphase.hip (the multi-phase driver). Not part of the
+// C-ABI.
 #ifndef MINIVITE_COARSEN_H
 #define MINIVITE_COARSEN_H
 
@@ -32,7 +33,7 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
 void mv_coarse_dev_free(mv_coarse_dev *c);
 
 // ---- building blocks shared with the distributed aggregation ----
-// Everything below is transport-free: engine.hip strings the pieces
+// Everything below is transport-free: multiphase.hip strings the pieces
 // together across the exchange seam. Each call works on `st`; the ones
 // that return host values or device allocations synchronise it.
 

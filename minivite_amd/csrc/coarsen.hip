@@ -25,8 +25,8 @@
 //
 // Steps 3 and 4 are one building block (mv_sort_reduce_keys) over a
 // caller-supplied key/weight array. The distributed aggregation (the
-// orchestration and every exchange live in engine.hip, next to the
-// transport seam) runs it twice — once over the local edges, once at the
+// orchestration and every exchange live in multiphase.hip, over
+// engine.hip's transport seam) runs it twice — once over the local edges, once at the
 // owner over the received per-rank partials — around the transport-free
 // pieces at the end of this file: sort-unique of global ids with the
 // scatter back through the sort permutation, owner-bucket bounds, the
@@ -468,8 +468,8 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
 }
 
 // ------------------------------------------------------------------------
-// Transport-free pieces of the distributed aggregation (engine.hip strings
-// them together across the seam; DESIGN.md, multi-phase section).
+// Transport-free pieces of the distributed aggregation (multiphase.hip
+// strings them together across the seam; DESIGN.md, multi-phase section).
 
 namespace {
 

@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/minivite_hip.h"
+#include "sweep_schedule.h"
 
 namespace {
 
@@ -579,6 +580,20 @@ int mv_degree_window_order(const int32_t *hint, const int64_t *xadj,
         }
     }
     return 0;
+}
+
+// The sweep's schedule arithmetic (header: mv_sweep_schedule), answered by
+// the functions the engine itself calls (sweep_schedule.h).
+int mv_sweep_schedule(int64_t lnv, int sweep_grid, int64_t window,
+                      int64_t positions, int unit, int launch_grid,
+                      int *default_unit, int64_t *default_row_group_out,
+                      int64_t *tickets) {
+    if (lnv < 0 || sweep_grid < 1 || window < 0 || positions < 0 ||
+        unit < 1 || launch_grid < 1)
+        return -1;
+    *default_unit = default_sweep_unit(lnv, sweep_grid);
+    *default_row_group_out = default_row_group(lnv, sweep_grid, window);
+    return queue_tickets(positions, unit, launch_grid, tickets);
 }
 
 } // extern "C"

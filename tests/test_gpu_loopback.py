@@ -1,7 +1,7 @@
 """Multi-rank HIP path on ONE GPU via the loopback transport.
 
 RCCL refuses two ranks on one device, so the p>1 engine code — the
-view-mode K4 sweeps (the MR=true instantiations of engine.hip's k4_sweep /
+view-mode K4 sweeps (the MR=true instantiations of sweep.hip's k4_sweep /
 k4_sweep_iter1 / k4_sweep_hi, and k4_sweep_lh), k8 community gathers, view builds, candidate filter +
 sort/unique, K9 replies, delta compaction, per-sender delta application,
 and the whole deep-pipelined per-iteration exchange protocol

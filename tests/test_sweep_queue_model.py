@@ -4,18 +4,23 @@ k4_sweep's RowQueue: the rows of a launch are cut into units of U rows,
 unit k = rows [kU, min((k+1)U, rows)). Wave x starts with unit x; the units
 from `waves` on are queued on `heads` ticket words, head h = block & (heads
 - 1), whose i-th ticket is queued unit i * heads + h. A wave stops at its
-first unit past the end. The host (mv_engine_run's take_queue) advances a
-running total per head by what the launch must consume and passes the old
-totals as bases; the words are never reset.
+first unit past the end. The host (take_queue in sweep.hip, with the figures
+of queue_tickets in sweep_schedule.h) advances a running total per head by
+what the launch must consume and passes the old totals as bases; the words
+are never reset.
 
 This model plays the kernel's loop for any number of blocks in any arrival
 order and checks: every row is walked exactly once and in order inside a
 unit, and every head's word advances by exactly the host's figure, launch
-after launch -- nu tickets per launch in all.
+after launch -- nu tickets per launch in all. The host's figure is restated
+here (heads_for / host_tickets) and checked against the library's own
+(mv_sweep_schedule), so the model vouches for the code that ships.
 """
 import random
 
 import pytest
+
+from minivite_amd import sweep_schedule
 
 QUEUE_HEADS = 8
 
@@ -107,3 +112,15 @@ def test_units_cover_rows_and_tickets_add_up(positions, unit, grid):
                 if a // unit == b // unit:
                     assert b == a + 1
         assert {r // unit for w in walked for r in w} == set(range(nu))
+
+
+@pytest.mark.parametrize("positions,unit,grid", CASES)
+def test_library_tickets_equal_the_model(positions, unit, grid):
+    """queue_tickets, the function take_queue calls, against the copy the
+    model above was checked with: head count, per-head additions, nu."""
+    rows = (positions + 63) // 64
+    _, _, add = sweep_schedule(positions, grid, positions=positions,
+                               unit=unit, launch_grid=grid)
+    assert len(add) == heads_for(grid)
+    assert add == host_tickets(rows, unit, grid)
+    assert sum(add) == (rows + unit - 1) // unit
