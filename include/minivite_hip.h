@@ -259,6 +259,12 @@ typedef struct {
                                * partition), and the identity variants of
                                * k4_sweep / k4_sweep_iter1, which never read
                                * the permutation, are the ones launched */
+    int64_t slot_bytes;       /* LDS bytes per slot and lane of the last
+                               * k4_sweep launch of the run: 8 on a unit
+                               * graph ({u32 key, u32 count}), 12 on a
+                               * weighted one (u32 key + f64 sum); 0 if no
+                               * k4_sweep ran. A launch counter like
+                               * `general`. */
 } mv_sweep_info;
 void mv_engine_get_sweep_info(const mv_engine *e, mv_sweep_info *out);
 

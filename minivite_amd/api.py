@@ -56,6 +56,7 @@ class MvSweepInfo(ctypes.Structure):
         ("sched_tickets", ctypes.c_int64),
         ("sched_tickets_expected", ctypes.c_int64),
         ("perm_identity", ctypes.c_int64),
+        ("slot_bytes", ctypes.c_int64),
     ]
 
 

@@ -356,6 +356,30 @@ __device__ __forceinline__ i64 load_in_place(const i64 *p) {
 // loads, so that it travels under the edge loop. The tails stay guarded by
 // deg: the SELL padding is never written and
 // a trailing slice of isolated vertices has width 0.
+//
+// Slots. A weighted lane keeps slot t as a f64 sum at sacc[t * B + tid] and a
+// u32 key at skey[t * B + tid]: 12 B, two LDS trips on a hit. On a unit graph
+// every accumulated weight is 1.0, so a slot sum is an integer count, exact
+// in any order, and (double)count carries the bits the f64 sum would: the
+// UNIT slot is one uint2 {key, count} at spair[t * B + tid] — 8 B, one
+// ds_read_b64 per probe, an integer add on a hit. The spill region keeps its
+// u32 keys and f64 sums in both forms.
+// UNIT also takes the self-loop test and the own-community sum out of the
+// ordered edge loop: each accumulator sees its own additions in the same
+// order wherever they are issued, so an unrolled pass over the chunk counts
+// both (as integers) and the rolled loop reads nothing but cb[j]. The
+// weighted body accumulates in edge order inside the loop, as the reference
+// does. The UNIT probe has no per-lane break: it reads the lane's ns slots
+// and keeps the match, and one masked store writes the hit's new count. A
+// wave walks its longest lane's slots either way; without the break the
+// exec-mask bookkeeping of the loop's two exits is gone (measured:
+// experiments/RESULTS.md, "Unit counts").
+constexpr int sweep_slot_bytes(bool unit) { return unit ? 8 : 12; }
+// dynamic LDS of a k4_sweep block: the launch and the occupancy query
+constexpr size_t sweep_lds_bytes(int slots, bool unit) {
+    return (size_t)slots * SWEEP_BLOCK * sweep_slot_bytes(unit);
+}
+
 template <bool MR, int SLOTS, bool UNIT, bool IDP>
 __global__ __launch_bounds__(SWEEP_BLOCK)
 __attribute__((amdgpu_waves_per_eu(UNIT ? 6 : 5)))
@@ -375,9 +399,11 @@ void k4_sweep(
     RowQueue queue) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int B = SWEEP_BLOCK;
+    // one of the two slot forms is live in an instantiation
     double *sacc = reinterpret_cast<double *>(smem);
     unsigned *skey =
         reinterpret_cast<unsigned *>(smem + sizeof(double) * SLOTS * B);
+    uint2 *spair = reinterpret_cast<uint2 *>(smem);
     const int tid = threadIdx.x;
     const i64 gthread = blockIdx.x * (i64)B + threadIdx.x;
     unsigned *myspill_k = spill_keys + spill_off[gthread];
@@ -402,6 +428,7 @@ void k4_sweep(
         } else {
             if (UNIT) vdeg = (double)deg;
             double c0 = 0.0, selfLoop = 0.0;
+            unsigned c0_n = 0, self_n = 0; // UNIT: the two sums as counts
             int ns = 0, nspill = 0;
             int tb[CH];
             double wb[CH];
@@ -411,24 +438,55 @@ void k4_sweep(
             for (int k0 = 0;;) {
                 unsigned cb[CH];
                 gather_comms<MR>(tb, lnv, vcurr, vghost, cb);
-                for (int j = 0; j < m; j++) {
-                    const i64 tidx = tb[j];
-                    const double w = UNIT ? 1.0 : wb[j];
-                    if (tidx == i) selfLoop += w; // dspl.hpp:247-248
-                    const unsigned tcomm = cb[j];
-                    if (tcomm == cc) { c0 += w; continue; }
-                    bool found = false;
-                    for (int t = 0; t < ns; t++) {
-                        if (skey[t * B + tid] == tcomm) {
-                            sacc[t * B + tid] += w;
-                            found = true;
-                            break;
-                        }
+                if constexpr (UNIT) {
+#pragma unroll
+                    for (int j = 0; j < CH; j++) {
+                        self_n += j < m && (i64)tb[j] == i; // dspl.hpp:247-248
+                        c0_n += j < m && cb[j] == cc;
                     }
-                    if (found) continue;
+                }
+                for (int j = 0; j < m; j++) {
+                    const double w = UNIT ? 1.0 : wb[j];
+                    const unsigned tcomm = cb[j];
+                    if constexpr (UNIT) {
+                        if (tcomm == cc) continue;
+                    } else {
+                        if ((i64)tb[j] == i) selfLoop += w; // :247-248
+                        if (tcomm == cc) { c0 += w; continue; }
+                    }
+                    bool found = false;
+                    if constexpr (UNIT) {
+                        // no break: scan the lane's ns slots, keep the match
+                        int hit = -1;
+                        unsigned hit_n = 0;
+                        for (int t = 0; t < ns; t++) {
+                            const uint2 p = spair[t * B + tid];
+                            if (p.x == tcomm) {
+                                hit = t;
+                                hit_n = p.y;
+                            }
+                        }
+                        if (hit >= 0) {
+                            spair[hit * B + tid].y = hit_n + 1;
+                            continue;
+                        }
+                    } else {
+                        for (int t = 0; t < ns; t++) {
+                            if (skey[t * B + tid] == tcomm) {
+                                sacc[t * B + tid] += w;
+                                found = true;
+                                break;
+                            }
+                        }
+                        if (found) continue;
+                    }
                     if (ns < SLOTS) {
-                        skey[ns * B + tid] = tcomm;
-                        sacc[ns * B + tid] = w;
+                        if constexpr (UNIT) {
+                            spair[ns * B + tid] = make_uint2(tcomm, 1u);
+                        } else {
+                            skey[ns * B + tid] = tcomm;
+                            sacc[ns * B + tid] = w;
+                        }
                         ns++;
                         continue;
                     }
@@ -450,6 +508,10 @@ void k4_sweep(
                 m = min(CH, deg - k0);
                 load_tails<UNIT>(ebase, k0, m, sell_tidx, sell_w, tb, wb);
             }
+            if constexpr (UNIT) { // counts of 1.0: the sums' exact bits
+                c0 = (double)c0_n;
+                selfLoop = (double)self_n;
+            }
             clusterWeight[i] = c0; // dspl.hpp:318 onto the K5-zeroed value
 
             // distGetMaxIndex: LDS slots first, then the spill in
@@ -461,10 +523,21 @@ void k4_sweep(
             double maxGain = 0.0;
             unsigned maxIndex = cc;
             i64 maxSize = cci.size;
-            for (int t = 0; t < ns; t++)
-                argmax_step<MR>(skey[t * B + tid], sacc[t * B + tid], eix,
-                                vdeg, ax, constant, lnv, base, sigma, cinfo,
-                                rc_ids, rc_info, maxGain, maxIndex, maxSize);
+            for (int t = 0; t < ns; t++) {
+                unsigned y;
+                double eiy;
+                if constexpr (UNIT) {
+                    const uint2 p = spair[t * B + tid];
+                    y = p.x;
+                    eiy = (double)p.y;
+                } else {
+                    y = skey[t * B + tid];
+                    eiy = sacc[t * B + tid];
+                }
+                argmax_step<MR>(y, eiy, eix, vdeg, ax, constant, lnv, base,
+                                sigma, cinfo, rc_ids, rc_info, maxGain,
+                                maxIndex, maxSize);
+            }
             for (int t = 0; t < nspill; t++)
                 argmax_step<MR>(myspill_k[t], myspill_a[t], eix, vdeg, ax,
                                 constant, lnv, base, sigma, cinfo, rc_ids,
@@ -845,9 +918,11 @@ RowQueue take_queue(mv_engine *e, i64 s0, i64 s1, int grid) {
 template <bool MR, int S, bool UNIT, bool IDP>
 void launch_sweep(const Sweep &w, i64 s0, i64 s1) {
     mv_engine *e = w.e;
-    const auto kernel = k4_sweep<MR, S, UNIT, IDP>; // S slots: 12 B/lane LDS
+    const auto kernel = k4_sweep<MR, S, UNIT, IDP>;
+    constexpr size_t lds = sweep_lds_bytes(S, UNIT); // S slots per lane
     e->sweep.general++;
     e->sweep.general_slots[mv_sweep_slot_index(S)]++;
+    e->sweep.slot_bytes = sweep_slot_bytes(UNIT);
     int grid = range_grid(e, s0, s1);
     if (w.queued) {
         // one resident round: a first unit on a block that starts late is
@@ -855,7 +930,7 @@ void launch_sweep(const Sweep &w, i64 s0, i64 s1) {
         int &per_cu = e->sweep_per_cu[mv_sweep_slot_index(S)][UNIT][IDP];
         if (!per_cu) { // once per engine and instantiation
             HIP_CHECK(hipOccupancyMaxActiveBlocksPerMultiprocessor(
-                &per_cu, kernel, 256, S * 256 * 12));
+                &per_cu, kernel, 256, lds));
             per_cu = std::max(per_cu, 1);
         }
         grid = std::min(grid, per_cu * e->num_cus);
@@ -863,7 +938,7 @@ void launch_sweep(const Sweep &w, i64 s0, i64 s1) {
     if (s1 == e->lnv) e->sched_grid = grid;
     // launches that do not queue: the static schedule on the full grid
     const RowQueue static_rows{nullptr, {}, e->row_group, 0};
-    kernel<<<grid, 256, S * 256 * 12, e->stream>>>(
+    kernel<<<grid, 256, lds, e->stream>>>(
         s0, s1, e->lnv, e->base, e->d_perm, e->d_deg, e->d_chunk_off,
         e->d_sell_tidx, e->d_sell_w, w.vcurr, e->d_vghost, e->d_vdeg,
         e->d_sigma, e->d_cinfo, e->d_cupd, e->d_rc_ids, e->d_rc_info,
