@@ -127,7 +127,7 @@ def split(csr, parts):
     for lo, hi in zip(parts[:-1], parts[1:]):
         out.append(((xadj[lo:hi + 1] - xadj[lo]).copy(),
                     tails[xadj[lo]:xadj[hi]].copy(),
-                    w[xadj[lo]:xadj[hi]].copy()))
+                    None if w is None else w[xadj[lo]:xadj[hi]].copy()))
     return out
 
 

@@ -1,6 +1,6 @@
 """Inputs for the unit-weight slot counts of k4_sweep. Shared by
 test_unit_counts_inputs_ref.py (CPU, pins the inputs with the oracle alone)
-and test_gpu_unit_counts.py / _unit_counts_child.py.
+and test_gpu_unit_counts.py / _engine_child.py.
 
 On a unit graph a k4_sweep slot is {u32 key, u32 count} and the self-loop
 and own-community sums are counted outside the ordered edge loop, one pass

@@ -4,57 +4,29 @@ MV_DEG_WINDOW / MV_DEG_QUANT are documented as "perf only, results
 identical": sigma carries the order, and k4_sweep / k4_sweep_iter1 hand each
 wave groups of rows instead of a grid stride. Every configuration here must
 reproduce the reference-pinned n=16384 RGG results (tests/golden/pins.json)
-exactly as test_gpu_sweep_switches checks them, while mv_sweep_info reports
+exactly as _gpu_run.check_vs_pin checks them, while mv_sweep_info reports
 the documented effective values and a smaller SELL image.
 
 An explicit MV_DEG_WINDOW is honoured as given (a window longer than lnv is
 reported as set and is one short window) with row_group = min(W/64, 8); the
 knobs are read at graph load, so they are set in-process and restored.
 """
-import os
-import threading
-
 import numpy as np
 import pytest
 
-import _sweep_child
-from test_gpu_sweep_switches import _check
+from _gpu_run import (check_rgg_pin, check_vs_oracle, knobs, run_ranks,
+                      run_rgg, traced_run)
+from _sweep_cases import tiny_csr
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("MV_DEG_WINDOW", "MV_DEG_QUANT")
 CONFIGS = [(1, True), (1, False), (2, True)]  # (world, unit)
 
 
-def _with_knobs(window, quant, fn):
-    """fn() with the knobs set (None: unset); the environment is restored.
-    Returns (fn's result, [sweep_info of every engine fn destroyed])."""
-    from minivite_amd import Engine
-    saved = {k: os.environ.get(k) for k in KNOBS}
-    infos, lock, destroy = [], threading.Lock(), Engine.destroy
-
-    def spy(self):
-        if getattr(self, "h", None):
-            with lock:
-                infos.append((self.rank, self.sweep_info()))
-        destroy(self)
-
-    try:
-        for k, v in zip(KNOBS, (window, quant)):
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        Engine.destroy = spy
-        out = fn()
-    finally:
-        Engine.destroy = destroy
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return out, [si for _, si in sorted(infos, key=lambda t: t[0])]
+def _run_windowed(window, quant, world, unit):
+    """The n=16384 RGG with the knobs set (None: unset) -> {rank: record}."""
+    with knobs(MV_DEG_WINDOW=window, MV_DEG_QUANT=quant):
+        return run_rgg(16384, world, unit)
 
 
 _plain = {}
@@ -63,8 +35,8 @@ _plain = {}
 def _plain_sell_entries(world, unit):
     """Per-rank SELL entries with the order off; one run per config."""
     if (world, unit) not in _plain:
-        _, infos = _with_knobs(0, None,
-                               lambda: _sweep_child.run(world, unit=unit))
+        records = _run_windowed(0, None, world, unit)
+        infos = [records[r]["sweep"] for r in range(world)]
         assert [si["deg_window"] for si in infos] == [0] * world
         assert [si["row_group"] for si in infos] == [1] * world
         _plain[(world, unit)] = [si["sell_entries"] for si in infos]
@@ -75,83 +47,58 @@ def _plain_sell_entries(world, unit):
 @pytest.mark.parametrize("window,quant", [(128, 1), (512, 4), (32768, 1)])
 def test_pins_hold_under_degree_windows(window, quant, world, unit):
     plain = _plain_sell_entries(world, unit)
-    out, infos = _with_knobs(window, quant,
-                             lambda: _sweep_child.run(world, unit=unit))
-    _check(out, world, unit)
-    assert len(infos) == world
-    for r, si in enumerate(infos):
+    records = _run_windowed(window, quant, world, unit)
+    check_rgg_pin(records, world, unit)
+    for r in range(world):
+        si = records[r]["sweep"]
         assert si["deg_window"] == window, f"rank {r}"
         assert si["deg_quant"] == quant, f"rank {r}"
         assert si["row_group"] == min(window // 64, 8), f"rank {r}"
         assert 0 < si["sell_entries"] < plain[r], f"rank {r}"
 
 
-def _tiny_csr(lnv):
-    """A chordal ring over the vertices that are not isolated (every 7th
-    is), with a self-loop on vertex 0. Rows ascending, symmetric."""
-    live = [v for v in range(lnv) if v % 7 != 3]
-    pairs = {(0, 0)}
-    for k, v in enumerate(live):
-        for step in (1, 3):
-            u = live[(k + step) % len(live)]
-            if u != v:
-                pairs.add((v, u))
-                pairs.add((u, v))
-    pairs = sorted(pairs)
-    xadj = np.zeros(lnv + 1, dtype=np.int64)
-    for v, _ in pairs:
-        xadj[v + 1] += 1
-    return np.cumsum(xadj), np.array([u for _, u in pairs], dtype=np.int64)
-
-
 @pytest.mark.parametrize("lnv", [1, 63, 65, 130])
 def test_tiny_from_csr_graphs_match_the_oracle(lnv):
     """Partial rows, a row that straddles the only window, isolated
     vertices and a self-loop; compared as test_gpu_parity compares."""
-    from minivite_amd import Graph, Engine
-    from oracle.oracle import OracleGraph, louvain, sha
-    xadj, tails = _tiny_csr(lnv)
+    from minivite_amd import Graph
+    from oracle.oracle import OracleGraph, louvain
+    xadj, tails = tiny_csr(lnv)
     parts = np.array([0, lnv], dtype=np.int64)
     og = OracleGraph.from_csr(lnv, 1, parts, [(xadj, tails, None)])
-    omod, oiters, ott, _ = louvain(og, trace=True)
+    oracle = louvain(og, trace=True)
     og.free()
 
-    def run():
+    def body(r, e):
         g = Graph.from_csr(lnv, 0, 1, parts, xadj, tails, None)
-        e = Engine(device=0)
-        e.load_graph(g)
-        e.set_trace(256)
-        mod, iters = e.run()
-        tt, _ = e.trace(iters)
+        rec, = traced_run(e, g, 256)
         has_hint = g.locality_hint() is not None
-        e.destroy()
         g.free()
-        return mod, iters, tt, has_hint
+        return rec, has_hint
 
-    (mod, iters, tt, has_hint), infos = _with_knobs(128, None, run)
+    with knobs(MV_DEG_WINDOW=128, MV_DEG_QUANT=None):
+        rec, has_hint = run_ranks(1, body)[0]
     # the order needs a hint, and a one-vertex graph gets none
-    assert infos[0]["deg_window"] == (128 if has_hint else 0)
-    assert infos[0]["row_group"] == (2 if has_hint else 1)
-    assert iters == oiters
-    assert float(mod).hex() == float(omod).hex()
-    for k in range(min(iters, 256)):
-        assert sha(tt[k]) == sha(ott[k]), f"iter {k + 1}"
+    assert rec["sweep"]["deg_window"] == (128 if has_hint else 0)
+    assert rec["sweep"]["row_group"] == (2 if has_hint else 1)
+    check_vs_oracle({0: rec}, oracle, parts)
 
 
 def test_default_routing_leaves_small_graphs_alone():
     """With no knob set a graph with at most one row per wave keeps the
     plain schedule: every existing small test runs exactly as before."""
-    from minivite_amd import Graph, Engine
+    from minivite_amd import Graph
 
-    def load():
+    def load(r, e):
         g = Graph.rgg(16384)
-        e = Engine(device=0)
         e.load_graph(g)
-        e.destroy()
+        si = e.sweep_info()
         g.free()
+        return si
 
-    _, infos = _with_knobs(None, None, load)
-    assert infos[0]["deg_window"] == 0
-    assert infos[0]["deg_quant"] == 1
-    assert infos[0]["row_group"] == 1
-    assert infos[0]["sell_entries"] > 0
+    with knobs(MV_DEG_WINDOW=None, MV_DEG_QUANT=None):
+        si = run_ranks(1, load)[0]
+    assert si["deg_window"] == 0
+    assert si["deg_quant"] == 1
+    assert si["row_group"] == 1
+    assert si["sell_entries"] > 0

@@ -13,14 +13,12 @@ exchange plan -- so a wrong full/compact comparison, an arm that never
 runs or a wrong candidate set fails even where the labels still come out
 right.
 """
-import os
-import threading
-
 import numpy as np
 import pytest
 
 import _halo_model as hm
 import _tie_graphs as tg
+from _gpu_run import check_vs_oracle, knobs, run_csrs
 from _multiphase_ref import phase_assignment
 
 pytestmark = pytest.mark.gpu
@@ -49,90 +47,21 @@ def _input(name, weights):
 
 # ---- running ----
 
-def _run_engines(csr, parts, nruns=1):
-    """One loopback engine per rank on device 0, `nruns` run() calls on the
-    same engines. -> per run {rank: dict(mod, iters, targets, mods,
-    communities, sweep, halo)}"""
-    from minivite_amd import Graph, Engine, LoopbackSession
-    world = len(parts) - 1
-    nv = int(parts[-1])
-    csrs = tg.split(csr, parts)
-    ses = LoopbackSession(world)
-    runs = [dict() for _ in range(nruns)]
-    errors = []
-
-    def rank_main(r):
-        try:
-            xa, ta, wa = csrs[r]
-            g = Graph.from_csr(nv, r, world, parts, xa, ta, wa)
-            e = Engine.loopback(ses, r, device=0)
-            e.load_graph(g)
-            e.set_trace(TRACE_CAP)
-            for results in runs:
-                mod, iters = e.run()
-                tt, tm = e.trace(iters)
-                results[r] = dict(
-                    mod=mod, iters=iters, targets=tt.copy(),
-                    mods=[float(m).hex() for m in tm],
-                    communities=e.communities(), sweep=e.sweep_info(),
-                    halo=e.halo_info(), lne=g.lne)
-            e.destroy()
-            g.free()
-        except Exception as ex:  # pragma: no cover
-            errors.append((r, repr(ex)))
-
-    threads = [threading.Thread(target=rank_main, args=(r,))
-               for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(timeout=120)
-    alive = [t for t in threads if t.is_alive()]
-    assert not alive, f"{len(alive)} rank threads still running"
-    ses.destroy()
-    assert not errors, errors
-    assert all(len(results) == world for results in runs)
-    return runs
-
-
 def _run_mode(csr, parts, mode, nruns=1):
-    var = MODES[mode]
-    if var is None:
-        return _run_engines(csr, parts, nruns)
-    saved = os.environ.get(var)
-    os.environ[var] = "1"
-    try:
-        return _run_engines(csr, parts, nruns)
-    finally:
-        if saved is None:
-            del os.environ[var]
-        else:
-            os.environ[var] = saved
+    """One loopback engine per rank on device 0, `nruns` run() calls on the
+    same engines -> [{rank: record} per run]."""
+    env = {MODES[mode]: "1"} if MODES[mode] else {}
+    with knobs(**env):
+        return run_csrs(tg.split(csr, parts), parts, TRACE_CAP, nruns,
+                        join_s=120)
 
 
 def _check(csr, parts, oracle, results, delta):
     """Everything a case asserts on every rank; -> the oracle's K."""
     world = len(parts) - 1
     nv = int(parts[-1])
-    omod, oiters, ott, otm = oracle
-    for r in range(world):
-        assert results[r]["iters"] == oiters, f"rank {r}"
-    full = np.zeros((oiters, nv), dtype=np.int64)
-    for r in range(world):
-        full[:, parts[r]:parts[r + 1]] = results[r]["targets"]
-    bad = np.argwhere(full != ott)
-    if bad.size:
-        k, v = bad[0]
-        pytest.fail(
-            f"{len(bad)} targets differ; first at iteration {k + 1} vertex "
-            f"{v} (degree {tg.degrees(csr)[v]}, rank "
-            f"{int(np.searchsorted(parts, v, 'right')) - 1}): engine "
-            f"{full[k, v]} oracle {ott[k, v]}")
-    for r in range(world):
-        assert float(results[r]["mod"]).hex() == float(omod).hex(), \
-            f"rank {r}"
-        assert results[r]["mods"] == [float(m).hex() for m in otm], \
-            f"rank {r}"
+    _, oiters, ott, _ = oracle
+    check_vs_oracle(results, oracle, parts, degrees=tg.degrees(csr))
     comm = np.concatenate([results[r]["communities"] for r in range(world)])
     assert np.array_equal(comm, phase_assignment(ott, oiters, nv))
     models = {ov: hm.halo_model(csr, parts, ott, bool(ov), delta)[0]

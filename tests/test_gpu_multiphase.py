@@ -11,12 +11,14 @@ between two summation orders of m positive doubles (each order is within
 import functools
 import json
 import os
-import threading
 
 import numpy as np
 import pytest
 
 import _multiphase_ref as ref
+from _coarsen_cases import (_assert_coarse_equal, _coarsen_case, _snap_equal,
+                            _snapshot, _weights)
+from _gpu_run import run_ranks
 
 pytestmark = pytest.mark.gpu
 
@@ -32,80 +34,12 @@ def _graph(csr):
                           tails, w)
 
 
-def _integral(w):
-    return bool(np.all(w == np.round(w)))
-
-
-def _assert_coarse_equal(got, fine, comm, gmap=None):
-    """got = (xadj, tails, w) from the GPU; fine = the aggregated graph."""
-    cx, ct, cw, cmap, runs = ref.coarsen(*fine, comm)
-    if gmap is not None:
-        assert np.array_equal(gmap, cmap)
-    assert np.array_equal(got[0], cx)
-    assert np.array_equal(got[1], ct)
-    if _integral(fine[2]):
-        assert np.array_equal(got[2], cw)
-        assert got[2].sum() == fine[2].sum()  # total weight conserved
-    else:
-        bound = (runs - 1) * 2.0 ** -52 * cw
-        assert np.all(np.abs(got[2] - cw) <= bound)
-
-
 # ---- 1. aggregation alone ----
-
-def _random_edges(rng, nv, m, lo=0):
-    """m random directed edges over vertices [lo, nv): self-loops and
-    parallel edges occur, vertices below lo stay isolated."""
-    return rng.integers(lo, nv, m), rng.integers(lo, nv, m)
-
-
-def _coarsen_case(name):
-    rng = np.random.default_rng(sum(map(ord, name)))
-    if name.startswith("nv"):
-        nv = int(name[2:])
-        u, v = _random_edges(rng, nv, 4 * nv)
-        return nv, u, v, rng.integers(0, nv, nv)
-    if name == "no_edges":
-        return 5, np.zeros(0, int), np.zeros(0, int), np.array([3, 3, 1, 0, 4])
-    if name == "one_community":
-        u, v = _random_edges(rng, 100, 600)
-        return 100, u, v, np.full(100, 7)
-    if name == "identity_parallel":
-        u, v = _random_edges(rng, 40, 2000)  # 1600 pairs: many repeats
-        return 40, u, v, np.arange(40)
-    if name == "sparse_unordered":
-        u, v = _random_edges(rng, 300, 2000)
-        return 300, u, v, rng.choice([299, 0, 17, 150, 3, 298], 300)
-    if name == "isolated_and_loops":
-        u, v = _random_edges(rng, 200, 900, lo=50)  # 0..49 isolated
-        loops = rng.integers(50, 200, 60)
-        return (200, np.r_[u, loops], np.r_[v, loops],
-                rng.integers(0, 200, 200))
-    if name == "community_of_1000":
-        u, v = _random_edges(rng, 1200, 8000)
-        return 1200, u, v, np.r_[np.full(1000, 5), np.arange(1000, 1200)]
-    if name == "parallel_5000":
-        u = np.r_[np.zeros(5000, int), np.ones(5000, int)]
-        return 2, u, 1 - u, np.array([1, 0])
-    if name == "random_3000":
-        u, v = _random_edges(rng, 3000, 40000)
-        return 3000, u, v, rng.integers(0, 200, 3000) * 7
-    raise KeyError(name)
-
 
 COARSEN_CASES = ["nv1", "nv2", "nv63", "nv64", "nv65", "nv257", "no_edges",
                  "one_community", "identity_parallel", "sparse_unordered",
                  "isolated_and_loops", "community_of_1000", "parallel_5000",
                  "random_3000"]
-
-
-def _weights(mode, m, seed):
-    rng = np.random.default_rng(seed)
-    if mode == "unit":
-        return np.ones(m)
-    if mode == "int":
-        return rng.integers(1, 9, m).astype(np.float64)
-    return rng.uniform(0.01, 1.0, m)
 
 
 @pytest.mark.parametrize("name", COARSEN_CASES)
@@ -216,35 +150,22 @@ def test_communities_before_a_run_raises():
 
 
 def test_communities_loopback_p2():
-    from minivite_amd import Graph, Engine, LoopbackSession
+    from minivite_amd import Graph
     from oracle.oracle import OracleGraph, louvain
     nv, world = 16384, 2
     og = OracleGraph.rgg(nv, world)
     _, oiters, ott, _ = louvain(og, trace=True)
     og.free()
-    ses = LoopbackSession(world)
-    results, errors = {}, []
 
-    def rank_main(r):
-        try:
-            g = Graph.rgg(nv, r, world)
-            e = Engine.loopback(ses, r, device=0)
-            e.load_graph(g)
-            _, iters = e.run()
-            results[r] = (iters, e.communities())
-            e.destroy()
-            g.free()
-        except Exception as ex:  # pragma: no cover
-            errors.append((r, repr(ex)))
+    def body(r, e):  # no trace armed
+        g = Graph.rgg(nv, r, world)
+        e.load_graph(g)
+        _, iters = e.run()
+        res = (iters, e.communities())
+        g.free()
+        return res
 
-    threads = [threading.Thread(target=rank_main, args=(r,))
-               for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(timeout=600)
-    ses.destroy()
-    assert not errors, errors
+    results = run_ranks(world, body, join_s=600)
     assert results[0][0] == results[1][0] == oiters >= 3
     full = np.concatenate([results[r][1] for r in range(world)])
     assert np.array_equal(full, ott[oiters - 3])
@@ -321,18 +242,6 @@ def _mp_input(name):
     return ref.adversarial(int(name[3:]))
 
 
-def _snapshot(h):
-    """Copy a Hierarchy out into plain Python/numpy data."""
-    L = h.levels
-    return dict(
-        phases=h.phases, levels=L,
-        graphs=[None] + [h.graph(k).arrays() for k in range(1, L + 1)],
-        maps=[None] + [h.map(k) for k in range(1, L + 1)],
-        q=[h.modularity(k) for k in range(L + 1)],
-        info=[None] + [h.phase_info(p) for p in range(1, h.phases + 1)],
-        communities=h.communities)
-
-
 def _run_mp(csr, max_phases=0, engine=None):
     from minivite_amd import Engine
     g = _graph(csr)
@@ -349,19 +258,6 @@ def _run_mp(csr, max_phases=0, engine=None):
 @functools.lru_cache(maxsize=None)
 def _mp_gpu(name):
     return _run_mp(_mp_input(name))
-
-
-def _snap_equal(a, b):
-    def same(x, y):
-        if isinstance(x, dict):
-            return all(same(x[k], y[k]) for k in x
-                       if k not in ("run_ms", "coarsen_ms"))
-        if isinstance(x, (list, tuple)):
-            return len(x) == len(y) and all(same(p, q) for p, q in zip(x, y))
-        if isinstance(x, np.ndarray):
-            return x.tobytes() == y.tobytes()
-        return x == y
-    return same(a, b)
 
 
 @pytest.mark.parametrize("name", MP_INPUTS)

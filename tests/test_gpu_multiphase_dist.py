@@ -4,9 +4,9 @@ alone (G2), the distributed driver against the host model of
 _multiphase_dist_ref.py (G3), its degenerate and hygiene cases (G4) and
 one run over real RCCL (G5, needs two devices).
 
-Ranks are loopback engines on device 0, one daemon thread per rank; a
-thread still alive after the join timeout fails the test, so mismatched
-collectives cannot wedge pytest.
+Ranks are loopback engines on device 0, one daemon thread per rank
+(_gpu_run.run_ranks); a thread still alive after the join timeout ends the
+pytest session, so mismatched collectives cannot wedge it.
 
 Weight rule for an aggregated graph, as in test_gpu_multiphase.py: offsets,
 tails, map and parts exact; weights exact when the fine weights are
@@ -16,8 +16,6 @@ positive doubles, the two-stage order (per rank, then rank order)
 included."""
 import functools
 import json
-import os
-import threading
 
 import numpy as np
 import pytest
@@ -25,10 +23,13 @@ import pytest
 import _multiphase_dist_ref as dref
 import _multiphase_ref as ref
 import _tie_graphs as tg
+from _coarsen_cases import (_assert_coarse_equal, _coarsen_case, _snap_equal,
+                            _snapshot, _weights)
+from _gpu_run import (GOLDEN, check_vs_oracle, check_vs_pin, run_csrs,
+                      run_ranks, traced_run)
 
 pytestmark = pytest.mark.gpu
 
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden", "pins.json")
 THRESH = dref.THRESH
 TRACE_CAP = 64
 JOIN_S = 120
@@ -37,29 +38,7 @@ JOIN_S = 120
 # ---- running ----
 
 def _run_ranks(world, body):
-    """body(rank, engine) on one loopback engine per rank -> {rank: value}."""
-    from minivite_amd import Engine, LoopbackSession
-    ses = LoopbackSession(world)
-    out, errors = {}, []
-
-    def rank_main(r):
-        try:
-            e = Engine.loopback(ses, r, device=0)
-            out[r] = body(r, e)
-            e.destroy()
-        except Exception as ex:
-            errors.append((r, repr(ex)))
-
-    threads = [threading.Thread(target=rank_main, args=(r,), daemon=True)
-               for r in range(world)]
-    for t in threads:
-        t.start()
-    for t in threads:
-        t.join(timeout=JOIN_S)
-    alive = [t for t in threads if t.is_alive()]
-    assert not alive, f"{len(alive)} rank threads still running"
-    ses.destroy()
-    return out, errors
+    return run_ranks(world, body, join_s=JOIN_S)
 
 
 def _slice(csr, parts, r):
@@ -79,26 +58,6 @@ def _stitch(slices):
             np.concatenate([s[2] for s in slices]))
 
 
-def _integral(w):
-    return bool(np.all(w == np.round(w)))
-
-
-def _assert_coarse_equal(got, fine, comm, gmap=None):
-    """got = the stitched (xadj, tails, w) from the GPU; fine = the
-    stitched aggregated graph."""
-    cx, ct, cw, cmap, runs = ref.coarsen(*fine, comm)
-    if gmap is not None:
-        assert np.array_equal(gmap, cmap)
-    assert np.array_equal(got[0], cx)
-    assert np.array_equal(got[1], ct)
-    if _integral(fine[2]):
-        assert np.array_equal(got[2], cw)
-        assert got[2].sum() == fine[2].sum()  # total weight conserved
-    else:
-        bound = (runs - 1) * 2.0 ** -52 * cw
-        assert np.all(np.abs(got[2] - cw) <= bound)
-
-
 # ---- G1: slices without vertices, single phase ----
 
 EMPTY_PARTS = {"tail": [0, 24, 24], "head": [0, 0, 24],
@@ -111,91 +70,21 @@ def test_empty_slice_single_phase(name, weights):
     csr = tg.WEIGHT_MODES[weights](ref.ring_of_cliques(6, 4))
     parts = np.array(EMPTY_PARTS[name], dtype=np.int64)
     world, nv = len(parts) - 1, int(parts[-1])
-    omod, oiters, ott, otm = tg.oracle_run(csr, world, parts,
-                                           trace_cap=TRACE_CAP)
-
-    def body(r, e):
-        g = _slice(csr, parts, r)
-        e.load_graph(g)
-        e.set_trace(TRACE_CAP)
-        mod, iters = e.run()
-        tt, tm = e.trace(iters)
-        res = dict(mod=mod, iters=iters, targets=tt.copy(),
-                   mods=[float(m).hex() for m in tm],
-                   communities=e.communities(), lnv=g.lnv)
-        g.free()
-        return res
-
-    out, errors = _run_ranks(world, body)
-    assert not errors, errors
+    oracle = tg.oracle_run(csr, world, parts, trace_cap=TRACE_CAP)
+    _, oiters, ott, _ = oracle
+    out, = run_csrs(tg.split(csr, parts), parts, TRACE_CAP, join_s=JOIN_S)
     assert sorted(out[r]["lnv"] for r in out) == sorted(np.diff(parts))
-    full = np.zeros((oiters, nv), dtype=np.int64)
-    for r in range(world):
-        assert out[r]["iters"] == oiters, f"rank {r}"
-        assert float(out[r]["mod"]).hex() == float(omod).hex(), f"rank {r}"
-        assert out[r]["mods"] == [float(m).hex() for m in otm], f"rank {r}"
-        full[:, parts[r]:parts[r + 1]] = out[r]["targets"]
-    assert np.array_equal(full, ott)
+    check_vs_oracle(out, oracle, parts)
     comm = np.concatenate([out[r]["communities"] for r in range(world)])
     assert np.array_equal(comm, ref.phase_assignment(ott, oiters, nv))
 
 
 # ---- G2: aggregation alone ----
 
-def _random_edges(rng, nv, m, lo=0):
-    """m random directed edges over vertices [lo, nv): self-loops and
-    parallel edges occur, vertices below lo stay isolated."""
-    return rng.integers(lo, nv, m), rng.integers(lo, nv, m)
-
-
-def _coarsen_case(name):
-    """The generator of test_gpu_multiphase.py's aggregation cases."""
-    rng = np.random.default_rng(sum(map(ord, name)))
-    if name.startswith("nv"):
-        nv = int(name[2:])
-        u, v = _random_edges(rng, nv, 4 * nv)
-        return nv, u, v, rng.integers(0, nv, nv)
-    if name == "no_edges":
-        return 5, np.zeros(0, int), np.zeros(0, int), np.array([3, 3, 1, 0, 4])
-    if name == "one_community":
-        u, v = _random_edges(rng, 100, 600)
-        return 100, u, v, np.full(100, 7)
-    if name == "identity_parallel":
-        u, v = _random_edges(rng, 40, 2000)  # 1600 pairs: many repeats
-        return 40, u, v, np.arange(40)
-    if name == "sparse_unordered":
-        u, v = _random_edges(rng, 300, 2000)
-        return 300, u, v, rng.choice([299, 0, 17, 150, 3, 298], 300)
-    if name == "isolated_and_loops":
-        u, v = _random_edges(rng, 200, 900, lo=50)  # 0..49 isolated
-        loops = rng.integers(50, 200, 60)
-        return (200, np.r_[u, loops], np.r_[v, loops],
-                rng.integers(0, 200, 200))
-    if name == "community_of_1000":
-        u, v = _random_edges(rng, 1200, 8000)
-        return 1200, u, v, np.r_[np.full(1000, 5), np.arange(1000, 1200)]
-    if name == "parallel_5000":
-        u = np.r_[np.zeros(5000, int), np.ones(5000, int)]
-        return 2, u, 1 - u, np.array([1, 0])
-    if name == "random_3000":
-        u, v = _random_edges(rng, 3000, 40000)
-        return 3000, u, v, rng.integers(0, 200, 3000) * 7
-    raise KeyError(name)
-
-
 COARSEN_CASES = ["nv1", "nv2", "nv65", "nv257", "no_edges", "one_community",
                  "identity_parallel", "sparse_unordered",
                  "isolated_and_loops", "community_of_1000", "parallel_5000",
                  "random_3000"]
-
-
-def _weights(mode, m, seed):
-    rng = np.random.default_rng(seed)
-    if mode == "unit":
-        return np.ones(m)
-    if mode == "int":
-        return rng.integers(1, 9, m).astype(np.float64)
-    return rng.uniform(0.01, 1.0, m)
 
 
 def _parts_kinds(nv, world):
@@ -218,8 +107,7 @@ def _coarsen_dist(world, jobs):
             g.free()
         return res
 
-    out, errors = _run_ranks(world, body)
-    assert not errors, errors
+    out = _run_ranks(world, body)
     results = []
     for j in range(len(jobs)):
         per = [out[r][j] for r in range(world)]
@@ -281,8 +169,7 @@ def test_coarsen_dist_bad_label_raises_on_every_rank(world, where, bad):
             g.free()
         return "returned"
 
-    out, errors = _run_ranks(world, body)
-    assert not errors, errors
+    out = _run_ranks(world, body)
     assert out == {r: "raised" for r in range(world)}
 
 
@@ -296,33 +183,6 @@ MP_CASES = [("ring30", 2, "even"), ("ring30", 3, "random"),
             ("rgg_w", 2, "even")]
 
 
-def _snapshot(h):
-    """Copy this rank's Hierarchy out into plain Python/numpy data."""
-    L = h.levels
-    return dict(
-        phases=h.phases, levels=L,
-        graphs=[None] + [h.graph(k).arrays() for k in range(1, L + 1)],
-        parts=[None] + [h.graph(k).parts for k in range(1, L + 1)],
-        nv=[None] + [h.graph(k).nv for k in range(1, L + 1)],
-        maps=[None] + [h.map(k) for k in range(1, L + 1)],
-        q=[h.modularity(k) for k in range(L + 1)],
-        info=[None] + [h.phase_info(p) for p in range(1, h.phases + 1)],
-        communities=h.communities)
-
-
-def _snap_equal(a, b):
-    def same(x, y):
-        if isinstance(x, dict):
-            return all(same(x[k], y[k]) for k in x
-                       if k not in ("run_ms", "coarsen_ms"))
-        if isinstance(x, (list, tuple)):
-            return len(x) == len(y) and all(same(p, q) for p, q in zip(x, y))
-        if isinstance(x, np.ndarray):
-            return x.tobytes() == y.tobytes()
-        return x == y
-    return same(a, b)
-
-
 def _run_dist(csr, parts, nruns=1, then=None):
     """nruns run_multiphase_dist calls on one set of engines -> per run
     {rank: snapshot}; then(rank, engine) runs afterwards on each rank."""
@@ -333,14 +193,13 @@ def _run_dist(csr, parts, nruns=1, then=None):
         snaps = []
         for _ in range(nruns):
             h = e.run_multiphase_dist(g, thresh=THRESH)
-            snaps.append(_snapshot(h))
+            snaps.append(_snapshot(h, dist=True))
             h.free()
         extra = then(r, e) if then else None
         g.free()
         return snaps, extra
 
-    out, errors = _run_ranks(world, body)
-    assert not errors, errors
+    out = _run_ranks(world, body)
     runs = [{r: out[r][0][k] for r in range(world)} for k in range(nruns)]
     return runs, {r: out[r][1] for r in range(world)}
 
@@ -450,7 +309,7 @@ def test_single_rank_dist_equals_run_multiphase(name):
     snaps = []
     for run in (e.run_multiphase, e.run_multiphase_dist):
         h = run(g, thresh=THRESH)
-        snaps.append(_snapshot(h))
+        snaps.append(_snapshot(h, dist=True))
         h.free()
     e.destroy()
     g.free()
@@ -464,33 +323,21 @@ def test_engine_reuse_after_multiphase_dist():
     """Two distributed runs on the same engines agree bit for bit, and a
     reload + plain run afterwards reproduces the two-rank phase-one pin."""
     from minivite_amd import Graph
-    from oracle.oracle import sha
     pin = json.load(open(GOLDEN))["rgg_n16384_p2_unit"]
     csr = dref.mp_input("rgg_unit")
     parts = tg.even_parts(16384, 2)
 
     def then(r, e):
         g = Graph.rgg(16384, r, 2)
-        e.load_graph(g)
-        e.set_trace(TRACE_CAP)
-        mod, iters = e.run()
-        tt, tm = e.trace(iters)
-        res = (mod, iters, tt.copy(), [float(m).hex() for m in tm])
+        rec, = traced_run(e, g, TRACE_CAP)
         g.free()
-        return res
+        return rec
 
     (a, b), after = _run_dist(csr, parts, nruns=2, then=then)
     for r in range(2):
         assert _snap_equal(a[r], b[r]), f"rank {r}"
         assert _snap_equal(a[r], _mp_gpu("rgg_unit", 2, "even")[1][r])
-    iters = after[0][1]
-    assert iters == after[1][1] == pin["iters"]
-    for r in range(2):
-        assert float(after[r][0]).hex() == pin["final_mod_hex"]
-        assert after[r][3] == pin["iter_mod_hex"]
-    for k in range(iters):
-        full = np.concatenate([after[r][2][k] for r in range(2)])
-        assert sha(full) == pin["iter_target_sha"][k], f"iteration {k + 1}"
+    check_vs_pin(after, pin)
 
 
 # ---- G5: real RCCL, two devices ----

@@ -11,19 +11,14 @@ bits, the targets of every iteration) or with the reference-pinned n=16384
 results, on inputs chosen for the branches of that code
 (_chain_graphs.py, pinned on the CPU by test_sweep_chain_inputs_ref.py).
 """
-import json
-import os
-import subprocess
-import sys
-
-import numpy as np
 import pytest
 
 import _chain_graphs as cg
-import _sweep_child
 import _tie_graphs as tg
-from test_gpu_sweep_queue import DEFAULT_UNIT_2M, _check_queue, _with_knobs
-from test_gpu_sweep_switches import _check
+from _gpu_run import (check_rgg_pin, check_vs_oracle, in_child, knobs,
+                      run_ranks, run_rgg, traced_run)
+from _sweep_cases import (DEFAULT_UNIT_2M, check_queue, queue_knobs,
+                          untraced_runs)
 
 pytestmark = pytest.mark.gpu
 
@@ -33,37 +28,22 @@ def _engine_vs_oracle(rem, mode, hint=False):
     (sweep_info, iterations, nv). Graph.from_csr derives a locality hint of
     its own unless MV_NO_BFS_HINT is set while it runs; without a hint the
     engine sorts the positions by descending degree."""
-    from minivite_amd import Graph, Engine
-    from oracle.oracle import sha
-    xadj, tails, w = tg.WEIGHT_MODES[mode](cg.chain_graph(rem))
+    from minivite_amd import Graph
+    xadj, tails, w = csr = tg.WEIGHT_MODES[mode](cg.chain_graph(rem))
     nv = len(xadj) - 1
-    omod, oiters, ott, _ = tg.oracle_run((xadj, tails, w))
-    parts = np.array([0, nv], dtype=np.int64)
-    saved = os.environ.get("MV_NO_BFS_HINT")
-    try:
-        if hint:
-            os.environ.pop("MV_NO_BFS_HINT", None)
-        else:
-            os.environ["MV_NO_BFS_HINT"] = "1"
-        g = Graph.from_csr(nv, 0, 1, parts, xadj, tails,
-                           None if mode == "unit" else w)
-    finally:
-        if saved is None:
-            os.environ.pop("MV_NO_BFS_HINT", None)
-        else:
-            os.environ["MV_NO_BFS_HINT"] = saved
-    e = Engine(device=0)
-    e.load_graph(g)
-    e.set_trace(64)
-    mod, iters = e.run()
-    tt, _ = e.trace(iters)
-    si = e.sweep_info()
-    e.destroy()
-    g.free()
-    assert iters == oiters
-    assert float(mod).hex() == float(omod).hex()
-    for k in range(iters):
-        assert sha(tt[k]) == sha(ott[k]), f"iter {k + 1}"
+    parts = tg.even_parts(nv, 1)
+
+    def body(r, e):
+        with knobs(MV_NO_BFS_HINT=None if hint else "1"):
+            g = Graph.from_csr(nv, 0, 1, parts, xadj, tails,
+                               None if mode == "unit" else w)
+        rec, = traced_run(e, g, 64)
+        g.free()
+        return rec
+
+    records = run_ranks(1, body)
+    iters = check_vs_oracle(records, tg.oracle_run(csr), parts)
+    si = records[0]["sweep"]
     assert si["unit_weights"] == (mode == "unit")
     assert si["skewed"] == 0 and si["perm_identity"] == int(hint)
     assert si["iter1_label_order"] + si["iter1_internal_order"] == 1
@@ -92,9 +72,9 @@ def test_hand_built_graph_on_one_block_with_the_queue(rem, mode):
     before, so a wrong ticket, base or head would run a row twice or not at
     all and the targets would differ from the oracle's. Over the
     degree-sorted order (no hint), with the partial last row at rem 1."""
-    (si, iters, nv), _ = _with_knobs(
-        3, 1, None, lambda: _engine_vs_oracle(rem, mode), queue_from=1)
-    _check_queue(si, 3)
+    with queue_knobs(3, 1, queue_from=1):
+        si, iters, nv = _engine_vs_oracle(rem, mode)
+    check_queue(si, 3)
     assert si["sched_grid"] == 1
     waves = 4
     units = ((nv + 63) // 64 + 2) // 3
@@ -104,41 +84,25 @@ def test_hand_built_graph_on_one_block_with_the_queue(rem, mode):
 
 
 def test_rgg_pin_runs_the_identity_variants():
-    out, infos = _with_knobs(None, None, None,
-                             lambda: _sweep_child.run(1, unit=True))
-    _check(out, 1, True)
-    assert infos[0]["perm_identity"] == 1
+    with queue_knobs(None, None):
+        records = run_rgg(16384, 1)
+    check_rgg_pin(records, 1)
+    assert records[0]["sweep"]["perm_identity"] == 1
 
 
 def test_rgg_2m_identity_variant_under_the_shipped_schedule():
-    from minivite_amd import Graph, Engine
-    from oracle.oracle import sha
-
-    def load():
-        g = Graph.rgg(1 << 21)
-        e = Engine(device=0)
-        e.load_graph(g)
-        res = []
-        for _ in range(2):
-            mod, iters = e.run()
-            res.append((float(mod).hex(), iters, sha(e.communities())))
-        e.destroy()
-        g.free()
-        return res
-
-    res, infos = _with_knobs(None, None, None, load)
-    si = infos[0]
+    res, si = untraced_runs(1 << 21, 2)
     assert si["perm_identity"] == 1
-    _check_queue(si, DEFAULT_UNIT_2M)
+    check_queue(si, DEFAULT_UNIT_2M)
     assert res[0] == res[1]
 
 
 def test_loopback_exports_first_order_is_not_the_identity():
-    out, infos = _with_knobs(None, None, None,
-                             lambda: _sweep_child.run(2, unit=True))
-    _check(out, 2, True)
-    assert len(infos) == 2
-    for r, si in enumerate(infos):
+    with queue_knobs(None, None):
+        records = run_rgg(16384, 2)
+    check_rgg_pin(records, 2)
+    for r in range(2):
+        si = records[r]["sweep"]
         # both ranks of this split export vertices and the loopback
         # transport always has a second channel, so the overlap and with it
         # the exports-first order are on: the check below is never vacuous
@@ -152,9 +116,6 @@ def test_spill_loop_after_the_scan_split(unit):
     """Four slots in every k4_sweep launch (iteration 2 on): most lanes of
     the first launches overflow into the spill, which the gain scan now
     reads in a loop of its own. The knobs are read once per process."""
-    env = dict(os.environ, MV_SLOTS="4", MV_SLOTS_FIRST="4")
-    child = subprocess.run(
-        [sys.executable, _sweep_child.__file__, "1", "unit" if unit else "w"],
-        env=env, capture_output=True, text=True, timeout=120)
-    assert child.returncode == 0, child.stderr[-2000:]
-    _check(json.loads(child.stdout.strip().splitlines()[-1]), 1, unit)
+    records = in_child(f"rgg:16384:{'unit' if unit else 'w'}", 1,
+                       {"MV_SLOTS": "4", "MV_SLOTS_FIRST": "4"})
+    check_rgg_pin(records, 1, unit)

@@ -5,70 +5,26 @@ identical": with a unit of U rows the waves of k4_sweep take their rows
 (after a first unit each) from ticket queues instead of a fixed schedule,
 and which wave runs which vertex changes from launch to launch. Every
 configuration here must reproduce the reference-pinned n=16384 RGG results
-(tests/golden/pins.json) exactly as test_gpu_sweep_switches checks them, and
+(tests/golden/pins.json) exactly as _gpu_run.check_vs_pin checks them, and
 mv_sweep_info must show that every launch drained its queues and no wave
 pulled past its first dry ticket: the device ticket words sum to the host's
 running total.
 
 The knobs are read at graph load, so they are set in-process and restored
-(as test_gpu_degree_windows does for its own).
+(_gpu_run.knobs).
 """
-import os
-import threading
-
 import numpy as np
 import pytest
 
-import _sweep_child
-from test_gpu_degree_windows import _tiny_csr
-from test_gpu_sweep_switches import _check
+import _tie_graphs as tg
+from _gpu_run import (check_rgg_pin, check_vs_oracle, run_ranks, run_rgg,
+                      traced_run)
+from _sweep_cases import (DEFAULT_UNIT_2M, check_queue, parity_case,
+                          queue_knobs, tiny_csr, untraced_runs)
 
 pytestmark = pytest.mark.gpu
 
-KNOBS = ("MV_SWEEP_UNIT", "MV_SWEEP_GRID", "MV_DEG_WINDOW",
-         "MV_SWEEP_QUEUE_FROM")
 CONFIGS = [(1, True), (1, False), (2, True)]  # (world, unit)
-DEFAULT_UNIT_2M = 2  # choose_row_queue's rule at n=2^21 (4 rows per wave)
-
-
-def _with_knobs(unit, grid, window, fn, queue_from=None):
-    """fn() with the knobs set (None: unset); the environment is restored.
-    Returns (fn's result, [sweep_info of every engine fn destroyed])."""
-    from minivite_amd import Engine
-    saved = {k: os.environ.get(k) for k in KNOBS}
-    infos, lock, destroy = [], threading.Lock(), Engine.destroy
-
-    def spy(self):
-        if getattr(self, "h", None):
-            with lock:
-                infos.append((self.rank, self.sweep_info()))
-        destroy(self)
-
-    try:
-        for k, v in zip(KNOBS, (unit, grid, window, queue_from)):
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = str(v)
-        Engine.destroy = spy
-        out = fn()
-    finally:
-        Engine.destroy = destroy
-        for k, v in saved.items():
-            if v is None:
-                os.environ.pop(k, None)
-            else:
-                os.environ[k] = v
-    return out, [si for _, si in sorted(infos, key=lambda t: t[0])]
-
-
-def _check_queue(si, unit, where=""):
-    assert si["sched_unit"] == unit, f"{where}{si}"
-    assert si["sched_tickets"] == si["sched_tickets_expected"], f"{where}{si}"
-    if unit:
-        assert si["sched_tickets"] > 0, f"{where}{si}"
-    else:
-        assert si["sched_tickets"] == 0, f"{where}{si}"
 
 
 # MV_SWEEP_GRID=8: 32 waves take the 256 rows (128 per rank at p=2), many
@@ -83,13 +39,12 @@ def _check_queue(si, unit, where=""):
 @pytest.mark.parametrize("U", [0, 1, 3, 8])
 def test_pins_hold_under_the_row_queue(U, grid, world, unit):
     window = 128 if (U, grid) == (3, 8) else None
-    out, infos = _with_knobs(U, grid, window,
-                             lambda: _sweep_child.run(world, unit=unit),
-                             queue_from=1)
-    _check(out, world, unit)
-    assert len(infos) == world
-    for r, si in enumerate(infos):
-        _check_queue(si, U, f"rank {r} ")
+    with queue_knobs(U, grid, window, queue_from=1):
+        records = run_rgg(16384, world, unit)
+    check_rgg_pin(records, world, unit)
+    for r in range(world):
+        si = records[r]["sweep"]
+        check_queue(si, U, f"rank {r} ")
         assert si["skewed"] == 0
         if grid:
             assert 0 < si["sched_grid"] <= grid, f"rank {r}"
@@ -106,37 +61,31 @@ def test_tiny_from_csr_graphs_match_the_oracle(lnv):
     """A partial last row, fewer units than waves (most tickets find the
     queue dry) and a range of a single position; compared as
     test_gpu_parity compares."""
-    from minivite_amd import Graph, Engine
-    from oracle.oracle import OracleGraph, louvain, sha
-    xadj, tails = _tiny_csr(lnv)
+    from minivite_amd import Graph
+    from oracle.oracle import OracleGraph, louvain
+    xadj, tails = tiny_csr(lnv)
     parts = np.array([0, lnv], dtype=np.int64)
     og = OracleGraph.from_csr(lnv, 1, parts, [(xadj, tails, None)])
-    omod, oiters, ott, _ = louvain(og, trace=True)
+    oracle = louvain(og, trace=True)
     og.free()
 
-    def run():
+    def body(r, e):
         g = Graph.from_csr(lnv, 0, 1, parts, xadj, tails, None)
-        e = Engine(device=0)
-        e.load_graph(g)
-        e.set_trace(256)
-        mod, iters = e.run()
-        tt, _ = e.trace(iters)
-        e.destroy()
+        rec, = traced_run(e, g, 256)
         g.free()
-        return mod, iters, tt
+        return rec
 
-    (mod, iters, tt), infos = _with_knobs(2, None, None, run, queue_from=1)
-    _check_queue(infos[0], 2)
+    with queue_knobs(2, None, queue_from=1):
+        records = run_ranks(1, body)
+    iters = check_vs_oracle(records, oracle, parts)
+    si = records[0]["sweep"]
+    check_queue(si, 2)
     rows = (lnv + 63) // 64
     # iteration 1 is the streaming kernel (static); every later one is a
     # k4_sweep launch of one block that takes a ticket per unit
-    assert iters >= 2 and infos[0]["general"] == iters - 1
-    assert infos[0]["sched_grid"] == 1
-    assert infos[0]["sched_tickets"] == (iters - 1) * ((rows + 1) // 2)
-    assert iters == oiters
-    assert float(mod).hex() == float(omod).hex()
-    for k in range(min(iters, 256)):
-        assert sha(tt[k]) == sha(ott[k]), f"iter {k + 1}"
+    assert iters >= 2 and si["general"] == iters - 1
+    assert si["sched_grid"] == 1
+    assert si["sched_tickets"] == (iters - 1) * ((rows + 1) // 2)
 
 
 @pytest.mark.parametrize("grid", [None, 8])
@@ -145,19 +94,16 @@ def test_skewed_graphs_keep_the_static_schedule(grid):
     vertices the static schedule hands it, so a queue asked for by name
     (MV_SWEEP_UNIT=2, from the first k4_sweep launch on) must still be
     refused: sched_unit reads 0, no ticket is taken or expected, and the
-    oracle's targets and modularity bits hold (test_gpu_tie_parity._case),
+    oracle's targets and modularity bits hold (_sweep_cases.parity_case),
     on the full grid and on a capped one whose threads each take many
     vertices."""
-    from test_gpu_tie_parity import _case, _input
-
-    def run():
-        return _case(_input("composite_relabelled"),
-                     {"skewed": 1, "sched_unit": 0, "sched_tickets": 0,
-                      "sched_tickets_expected": 0, "hi": "iters"})
-
-    results, _ = _with_knobs(2, grid, None, run, queue_from=1)
+    with queue_knobs(2, grid, queue_from=1):
+        records = parity_case(
+            tg.composite_relabelled(),
+            {"skewed": 1, "sched_unit": 0, "sched_tickets": 0,
+             "sched_tickets_expected": 0, "hi": "iters"})
     if grid:
-        assert 0 < results[0][4]["sched_grid"] <= grid
+        assert 0 < records[0]["sweep"]["sched_grid"] <= grid
 
 
 def test_repeatability_with_the_queue_on():
@@ -165,15 +111,13 @@ def test_repeatability_with_the_queue_on():
     every iteration do not."""
     outs = []
     for _ in range(2):
-        out, infos = _with_knobs(3, 8, None,
-                                 lambda: _sweep_child.run(1, unit=True),
-                                 queue_from=1)
-        _check_queue(infos[0], 3)
-        outs.append(out)
-    _check(outs[0], 1, True)
-    assert outs[0]["ranks"][0]["iter_mod_hex"] == \
-        outs[1]["ranks"][0]["iter_mod_hex"]
-    assert outs[0]["iter_target_sha"] == outs[1]["iter_target_sha"]
+        with queue_knobs(3, 8, queue_from=1):
+            records = run_rgg(16384, 1)
+        check_queue(records[0]["sweep"], 3)
+        outs.append(records)
+    check_rgg_pin(outs[0], 1)
+    assert outs[0][0]["mods"] == outs[1][0]["mods"]
+    assert np.array_equal(outs[0][0]["targets"], outs[1][0]["targets"])
 
 
 def test_default_unit():
@@ -181,26 +125,10 @@ def test_default_unit():
     of the full grid keeps the static schedule (n=16384: one row per wave),
     a larger one gets the derived unit (n=2^21: 32768 rows over 8192 waves
     -> U=2) on its steady launches only, and two runs of it agree."""
-    from minivite_amd import Graph, Engine
-    from oracle.oracle import sha
-
-    def load(nv, runs):
-        g = Graph.rgg(nv)
-        e = Engine(device=0)
-        e.load_graph(g)
-        res = []
-        for _ in range(runs):
-            mod, iters = e.run()
-            res.append((float(mod).hex(), iters, sha(e.communities())))
-        e.destroy()
-        g.free()
-        return res
-
-    _, infos = _with_knobs(None, None, None, lambda: load(16384, 0))
-    _check_queue(infos[0], 0)
-    res, infos = _with_knobs(None, None, None, lambda: load(1 << 21, 2))
-    si = infos[0]
-    _check_queue(si, DEFAULT_UNIT_2M)
+    _, si = untraced_runs(16384, 0)
+    check_queue(si, 0)
+    res, si = untraced_runs(1 << 21, 2)
+    check_queue(si, DEFAULT_UNIT_2M)
     assert res[0] == res[1]
     iters = res[0][1]
     assert iters > 2 and si["general"] == iters - 1
@@ -216,12 +144,11 @@ def test_default_unit_four_on_a_capped_grid():
     derives U=4 with no MV_SWEEP_UNIT set. Iterations 1 and 2 stay static;
     every later launch takes one ticket for each of its 64 units; the pins
     hold."""
-    out, infos = _with_knobs(None, 8, None,
-                             lambda: _sweep_child.run(1, unit=True))
-    _check(out, 1, True)
-    si = infos[0]
-    _check_queue(si, 4)
-    iters = out["ranks"][0]["iters"]
+    with queue_knobs(None, 8):
+        records = run_rgg(16384, 1)
+    iters = check_rgg_pin(records, 1)
+    si = records[0]["sweep"]
+    check_queue(si, 4)
     assert iters > 2
     assert si["sched_tickets"] == (iters - 2) * (256 // 4)
     assert 0 < si["sched_grid"] <= 8

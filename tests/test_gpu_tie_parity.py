@@ -14,22 +14,15 @@ iteration, vertex and that vertex's degree: degree > 256 is k4_sweep_hi
 (unit) / k4_sweep_lh (weighted), anything else k4_sweep_iter1 at
 iteration 1 and k4_sweep after it (sweep_info tells which instantiation).
 """
-import json
-import os
-import subprocess
-import sys
-import tempfile
-import threading
-
 import numpy as np
 import pytest
 
-import _tie_child
 import _tie_graphs as tg
+from _gpu_run import in_child
+from _sweep_cases import check_parity, check_routing, parity_case as _case
 
 pytestmark = pytest.mark.gpu
 
-TRACE_CAP = 64
 _CACHE = {}
 
 
@@ -40,108 +33,6 @@ def _input(name, mode="unit", shuffled=False):
         csr = tg.WEIGHT_MODES[mode](getattr(tg, name)())
         _CACHE[key] = tg.shuffle_rows(csr, 3) if shuffled else csr
     return _CACHE[key]
-
-
-# ---- running ----
-
-def _run_engines(csr, parts):
-    """One engine per rank (loopback on device 0 when there are several).
-    -> {rank: (mod, iters, targets, mod hexes, sweep_info)}"""
-    from minivite_amd import Graph, Engine, LoopbackSession
-    world = len(parts) - 1
-    nv = int(parts[-1])
-    csrs = tg.split(csr, parts)
-    ses = LoopbackSession(world) if world > 1 else None
-    results = {}
-    errors = []
-
-    def rank_main(r):
-        try:
-            xa, ta, wa = csrs[r]
-            g = Graph.from_csr(nv, r, world, parts, xa, ta, wa)
-            e = Engine.loopback(ses, r, device=0) if ses else Engine(device=0)
-            e.load_graph(g)
-            e.set_trace(TRACE_CAP)
-            mod, iters = e.run()
-            tt, tm = e.trace(iters)
-            results[r] = (mod, iters, tt.copy(),
-                          [float(m).hex() for m in tm], e.sweep_info())
-            e.destroy()
-            g.free()
-        except Exception as ex:  # pragma: no cover
-            errors.append((r, repr(ex)))
-
-    if world == 1:
-        rank_main(0)
-    else:
-        threads = [threading.Thread(target=rank_main, args=(r,))
-                   for r in range(world)]
-        for t in threads:
-            t.start()
-        for t in threads:
-            t.join(timeout=300)
-        ses.destroy()
-    assert not errors, errors
-    assert len(results) == world
-    return results
-
-
-def _check_parity(csr, parts, results):
-    """Iteration count, every target row, every modularity bit, on every
-    rank, against the oracle on the same partition of the same CSR."""
-    world = len(parts) - 1
-    nv = int(parts[-1])
-    omod, oiters, ott, otm = tg.oracle_run(csr, world, parts,
-                                           trace_cap=TRACE_CAP)
-    for r in range(world):
-        assert results[r][1] == oiters, f"rank {r}"
-    full = np.zeros((oiters, nv), dtype=np.int64)
-    for r in range(world):
-        full[:, parts[r]:parts[r + 1]] = results[r][2]
-    bad = np.argwhere(full != ott)
-    if bad.size:
-        k, v = bad[0]
-        deg = tg.degrees(csr)
-        pytest.fail(
-            f"{len(bad)} targets differ; first at iteration {k + 1} vertex "
-            f"{v} (degree {deg[v]}, rank "
-            f"{int(np.searchsorted(parts, v, 'right')) - 1}): engine "
-            f"{full[k, v]} oracle {ott[k, v]}")
-    assert np.array_equal(full, ott)
-    for r in range(world):
-        assert float(results[r][0]).hex() == float(omod).hex(), f"rank {r}"
-        assert results[r][3] == [float(m).hex() for m in otm], f"rank {r}"
-    return oiters
-
-
-def _check_routing(info, iters, expect, where=""):
-    """expect: {sweep_info key or ('slots', S): value}; a value is an int,
-    '>0', or 'iters' / 'iters-N' (relative to the run's iteration count)."""
-    for key, want in expect.items():
-        got = info["general_slots"][key[1]] if isinstance(key, tuple) \
-            else info[key]
-        if want == ">0":
-            assert got > 0, f"{where}{key}: {got}, expected > 0 -- {info}"
-            continue
-        if isinstance(want, str):
-            want = iters - int(want[len("iters-"):] or 0)
-        assert got == want, f"{where}{key}: {got}, expected {want} -- {info}"
-
-
-def _case(csr, expect, parts=None, rank_expect=None):
-    """Run, compare with the oracle, then check the routing: `expect` on
-    every rank, rank_expect[r] on rank r."""
-    nv = len(csr[0]) - 1
-    parts = tg.even_parts(nv, 1) if parts is None else \
-        np.asarray(parts, dtype=np.int64)
-    results = _run_engines(csr, parts)
-    iters = _check_parity(csr, parts, results)
-    for r in sorted(results):
-        _check_routing(results[r][4], iters, expect, f"rank {r} ")
-        if rank_expect:
-            _check_routing(results[r][4], iters, rank_expect[r],
-                           f"rank {r} ")
-    return results
 
 
 def _local_hubs(csr, parts):
@@ -269,7 +160,7 @@ def test_closed_rank():
                     rank_expect=[{"nghost": 0, "ssz": 0, "skewed": 0},
                                  {"nghost": ">0", "ssz": ">0", "skewed": 1},
                                  {"nghost": ">0", "ssz": ">0", "skewed": 0}])
-    overlap = [results[r][4]["overlap"] for r in range(3)]
+    overlap = [results[r]["sweep"]["overlap"] for r in range(3)]
     assert overlap[0] == overlap[1] == overlap[2], overlap
 
 
@@ -289,7 +180,7 @@ def test_dense_unit_p2():
                           "nexp": ">0", ("slots", 24): ">0"},
                     parts=tg.even_parts(len(csr[0]) - 1, 2))
     for r, res in results.items():
-        info = res[4]
+        info = res["sweep"]
         assert info["general"] == info["general_slots"][24], (r, info)
 
 
@@ -297,26 +188,13 @@ def test_dense_unit_p2():
 
 def test_lane_hash_unit():
     """MV_LH_THRESH is read once per process: a fresh child runs with the
-    lane-hash band widened to degree > 16 (the hubs stay wave-per-vertex)
-    and saves its trace."""
+    lane-hash band widened to degree > 16 (the hubs stay wave-per-vertex)."""
     csr = _input("composite_relabelled")
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.npz")
-        child = subprocess.run(
-            [sys.executable, _tie_child.__file__, path],
-            env=dict(os.environ, MV_LH_THRESH="16"),
-            capture_output=True, text=True, timeout=120)
-        assert child.returncode == 0, child.stderr[-2000:]
-        info = json.loads(child.stdout.strip().splitlines()[-1])
-        info["general_slots"] = {int(k): v for k, v in
-                                 info["general_slots"].items()}
-        z = np.load(path)
-        results = {0: (float(z["mod"]), int(z["iters"]), z["targets"],
-                       [float(m).hex() for m in z["mods"]], info)}
-    parts = tg.even_parts(len(csr[0]) - 1, 1)
-    iters = _check_parity(csr, parts, results)
+    results = in_child("tie:composite_relabelled", 1, {"MV_LH_THRESH": "16"})
+    info = results[0]["sweep"]
+    iters = check_parity(csr, tg.even_parts(len(csr[0]) - 1, 1), results)
     nband = int(np.sum(tg.degrees(csr) > 16))
     assert nband > 10
-    _check_routing(info, iters, {"nhi": 10, "nlh": nband, "hi": "iters",
-                                 "lh": "iters", "unit_weights": 1,
-                                 "skewed": 1})
+    check_routing(info, iters, {"nhi": 10, "nlh": nband, "hi": "iters",
+                                "lh": "iters", "unit_weights": 1,
+                                "skewed": 1})

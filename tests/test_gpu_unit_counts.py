@@ -9,21 +9,14 @@ are exact: each case demands the oracle's targets and its modularity bits
 for every iteration, and asserts slot_bytes and general_slots from
 Engine.sweep_info(), so that it cannot pass on another kernel.
 
-The knobs that are read once per process go through _unit_counts_child.py.
+The knobs that are read once per process go through _gpu_run.in_child().
 """
-import json
-import os
-import subprocess
-import sys
-import tempfile
-
-import numpy as np
 import pytest
 
 import _tie_graphs as tg
 import _unit_count_graphs as ug
-import _unit_counts_child
-from test_gpu_tie_parity import _check_parity, _check_routing, _run_engines
+from _gpu_run import in_child
+from _sweep_cases import check_parity, check_routing, run_parity
 
 pytestmark = pytest.mark.gpu
 
@@ -32,39 +25,20 @@ FOUR_SLOTS = {"MV_SLOTS": "4", "MV_SLOTS_FIRST": "4", "MV_NO_ITER1": "1"}
 
 def _in_process(name, mode, expect):
     csr = ug.graph(name, mode)
-    parts = tg.even_parts(len(csr[0]) - 1, 1)
-    results = _run_engines(csr, parts)
-    iters = _check_parity(csr, parts, results)
-    _check_routing(results[0][4], iters, expect)
-    return iters, results[0][4]
+    results, iters = run_parity(csr, tg.even_parts(len(csr[0]) - 1, 1))
+    check_routing(results[0]["sweep"], iters, expect)
+    return iters, results[0]["sweep"]
 
 
 def _in_child(name, mode, world, env, expect):
     """A fresh process with `env` set; the oracle runs here."""
     csr = ug.graph(name, mode)
     parts = tg.even_parts(len(csr[0]) - 1, world)
-    with tempfile.TemporaryDirectory() as d:
-        path = os.path.join(d, "trace.npz")
-        child = subprocess.run(
-            [sys.executable, _unit_counts_child.__file__, name, mode,
-             str(world), path],
-            env=dict(os.environ, **env), capture_output=True, text=True,
-            timeout=120)
-        assert child.returncode == 0, child.stderr[-2000:]
-        out = json.loads(child.stdout.strip().splitlines()[-1])
-        z = np.load(path)
-        results = {}
-        for r in range(world):
-            o = out[str(r)]
-            info = o["info"]
-            info["general_slots"] = {int(k): v for k, v in
-                                     info["general_slots"].items()}
-            results[r] = (float.fromhex(o["mod"]), o["iters"],
-                          z[f"targets{r}"], o["mods"], info)
-    iters = _check_parity(csr, parts, results)
+    results = in_child(f"unitcount:{name}:{mode}", world, env)
+    iters = check_parity(csr, parts, results)
     for r in range(world):
-        _check_routing(results[r][4], iters, expect, f"rank {r} ")
-    return iters, [results[r][4] for r in range(world)]
+        check_routing(results[r]["sweep"], iters, expect, f"rank {r} ")
+    return iters, [results[r]["sweep"] for r in range(world)]
 
 
 # skewed p == 1 with unsorted rows: k4_sweep runs every iteration, 12 slots
