@@ -1,22 +1,22 @@
 // coarsen.h — internal seam between coarsen.hip (the community-aggregation
 // kernels) and multiphase.hip (the multi-phase driver). Not part of the
-// C-ABI.
+// C-ABI. The result structs own their device memory (DevBuf members, so
+// they are move-only): whoever holds one returns on any path without
+// clean-up.
 #ifndef MINIVITE_COARSEN_H
 #define MINIVITE_COARSEN_H
 
-#include <cstdint>
-
-#include <hip/hip_runtime.h>
+#include "device_util.h"
 
 // Device-resident result of one aggregation. d_map is always set; the CSR
 // arrays stay null when the call stopped after renumbering.
 struct mv_coarse_dev {
-    int64_t nc = 0;            // coarse vertices
-    int64_t ne = 0;            // coarse directed edges (distinct pairs)
-    int64_t *d_map = nullptr;  // nv: fine vertex -> dense coarse id
-    int64_t *d_xadj = nullptr; // nc+1
-    int64_t *d_tails = nullptr; // ne, ascending within a row
-    double *d_w = nullptr;      // ne
+    int64_t nc = 0;          // coarse vertices
+    int64_t ne = 0;          // coarse directed edges (distinct pairs)
+    DevBuf<int64_t> d_map;   // nv: fine vertex -> dense coarse id
+    DevBuf<int64_t> d_xadj;  // nc+1
+    DevBuf<int64_t> d_tails; // ne, ascending within a row
+    DevBuf<double> d_w;      // ne
 };
 
 // Aggregate the single-rank device CSR (xadj/tails; d_w null = unit
@@ -30,8 +30,6 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
                       const double *d_w, const int64_t *d_labels,
                       bool stop_if_identity, mv_coarse_dev *out);
 
-void mv_coarse_dev_free(mv_coarse_dev *c);
-
 // ---- building blocks shared with the distributed aggregation ----
 // Everything below is transport-free: multiphase.hip strings the pieces
 // together across the exchange seam. Each call works on `st`; the ones
@@ -40,10 +38,9 @@ void mv_coarse_dev_free(mv_coarse_dev *c);
 // One (key, summed weight) per distinct key, keys ascending.
 struct mv_key_runs {
     int64_t n = 0;
-    uint64_t *d_key = nullptr; // never null after the call
-    double *d_w = nullptr;
+    DevBuf<uint64_t> d_key; // neither is null after the call
+    DevBuf<double> d_w;
 };
-void mv_key_runs_free(mv_key_runs *r);
 
 // Stable radix sort of n (key, weight) pairs over the low `bits` key bits,
 // run heads, and the fixed-order run reduction (<= 32 entries left to
@@ -58,11 +55,10 @@ void mv_sort_reduce_keys(hipStream_t st, int64_t n, const uint64_t *d_keys,
 // back: input position d_perm[i] holds the id of run d_run[i].
 struct mv_unique_ids {
     int64_t n = 0, nuniq = 0;
-    int64_t *d_uniq = nullptr; // nuniq ids, ascending
-    unsigned *d_perm = nullptr; // n: sorted position -> input position
-    unsigned *d_run = nullptr;  // n: sorted position -> index into d_uniq
+    DevBuf<int64_t> d_uniq; // nuniq ids, ascending
+    DevBuf<unsigned> d_perm; // n: sorted position -> input position
+    DevBuf<unsigned> d_run;  // n: sorted position -> index into d_uniq
 };
-void mv_unique_ids_free(mv_unique_ids *u);
 void mv_sort_unique_ids(hipStream_t st, int64_t n, const int64_t *d_ids,
                         int bits, mv_unique_ids *out);
 // d_out[input position] = d_vals[index of its id in d_uniq]

@@ -32,52 +32,22 @@
 // scatter back through the sort permutation, owner-bucket bounds, the
 // owner-side gather / mark / dense-id kernels, and the key kernel with the
 // local / remote tail split.
+//
+// Device memory, the binary search, the iota and bounds kernels are
+// device_util.h's and every hipCUB call goes through cub_util.h: the same
+// ones the engine uses. Nothing here needs RCCL or the engine's structs.
 
-#include <algorithm>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
 #include <vector>
-
-#include <hip/hip_runtime.h>
-#include <hipcub/hipcub.hpp>
 
 #include "../../include/minivite_hip.h"
 #include "coarsen.h"
-
-#define HIP_CHECK(x)                                                          \
-    do {                                                                      \
-        hipError_t _e = (x);                                                  \
-        if (_e != hipSuccess) {                                               \
-            std::fprintf(stderr, "HIP error %s at %s:%d: %s\n",               \
-                         hipGetErrorString(_e), __FILE__, __LINE__, #x);      \
-            std::abort();                                                     \
-        }                                                                     \
-    } while (0)
+#include "cub_util.h"
 
 namespace {
 
-using i64 = int64_t;
 using u64 = unsigned long long;
 
 constexpr int kShortRun = 32; // longest run one thread sums on its own
-
-int grid_for(i64 n, int block = 256, int cap = 2048) {
-    i64 g = (n + block - 1) / block;
-    return (int)std::min<i64>(std::max<i64>(g, 1), cap);
-}
-
-// scratch allocation freed at scope exit (never null: floors at 1 element)
-template <class T> struct Scratch {
-    T *ptr = nullptr;
-    explicit Scratch(i64 n) {
-        HIP_CHECK(hipMalloc((void **)&ptr, sizeof(T) * std::max<i64>(n, 1)));
-    }
-    ~Scratch() { (void)hipFree(ptr); }
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    operator T *() const { return ptr; }
-};
 
 // ---- 1. renumber ----
 // used[l] = 1 for every label in use; a label outside [0,nv) raises *err
@@ -176,16 +146,9 @@ __global__ void k_coarse_rows(i64 row0, i64 nc, i64 nruns, int shift,
     const i64 n = nruns > nc + 1 ? nruns : nc + 1;
     for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
          i += (i64)gridDim.x * blockDim.x) {
-        if (i <= nc) {
-            const u64 key = (u64)(row0 + i) << shift;
-            i64 lo = 0, hi = nruns;
-            while (lo < hi) {
-                const i64 mid = (lo + hi) >> 1;
-                if (run_key[mid] < key) lo = mid + 1;
-                else hi = mid;
-            }
-            cxadj[i] = lo;
-        }
+        if (i <= nc)
+            cxadj[i] = dev_lower_bound(run_key, nruns,
+                                       (u64)(row0 + i) << shift);
         if (i < nruns) ctails[i] = (i64)(run_key[i] & mask);
     }
 }
@@ -243,78 +206,44 @@ __global__ __launch_bounds__(256) void k_reduce_long(
     }
 }
 
-// exclusive prefix sum of n unsigned values (n < 2^31)
-void exclusive_sum(hipStream_t st, const unsigned *in, unsigned *out, i64 n) {
-    size_t bytes = 0;
-    (void)hipcub::DeviceScan::ExclusiveSum(nullptr, bytes, in, out, (int)n,
-                                           st);
-    Scratch<char> tmp((i64)bytes);
-    HIP_CHECK(hipcub::DeviceScan::ExclusiveSum(tmp.ptr, bytes, in, out,
-                                               (int)n, st));
-    HIP_CHECK(hipStreamSynchronize(st)); // tmp dies with this scope
-}
-
 } // namespace
-
-void mv_key_runs_free(mv_key_runs *r) {
-    if (r->d_key) (void)hipFree(r->d_key);
-    if (r->d_w) (void)hipFree(r->d_w);
-    *r = mv_key_runs{};
-}
 
 void mv_sort_reduce_keys(hipStream_t st, int64_t n, const uint64_t *d_keys_in,
                          const double *d_w, int bits, mv_key_runs *out) {
     *out = mv_key_runs{};
-    if (n == 0) { // never-null outputs, no zero-length hipCUB calls
-        HIP_CHECK(hipMalloc((void **)&out->d_key, 8));
-        HIP_CHECK(hipMalloc((void **)&out->d_w, 8));
+    if (n == 0) { // never-null outputs
+        out->d_key.reserve(0);
+        out->d_w.reserve(0);
         return;
     }
     const u64 *keys = (const u64 *)d_keys_in;
     // ---- 3. sort over the live key bits ----
-    Scratch<u64> ks(n);
-    Scratch<double> ws(d_w ? n : 0);
-    {
-        size_t bytes = 0;
-        if (d_w)
-            (void)hipcub::DeviceRadixSort::SortPairs(
-                nullptr, bytes, keys, ks.ptr, d_w, ws.ptr, (int)n, 0, bits,
-                st);
-        else
-            (void)hipcub::DeviceRadixSort::SortKeys(
-                nullptr, bytes, keys, ks.ptr, (int)n, 0, bits, st);
-        Scratch<char> tmp((i64)bytes);
-        if (d_w)
-            HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-                tmp.ptr, bytes, keys, ks.ptr, d_w, ws.ptr, (int)n, 0, bits,
-                st));
-        else
-            HIP_CHECK(hipcub::DeviceRadixSort::SortKeys(
-                tmp.ptr, bytes, keys, ks.ptr, (int)n, 0, bits, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
+    DevBuf<u64> ks(n);
+    DevBuf<double> ws(d_w ? n : 0);
+    DevBuf<char> tmp; // freed at return: every path below synchronises
+    if (d_w)
+        cub_sort_pairs(tmp, st, keys, ks.get(), d_w, ws.get(), n, bits);
+    else
+        cub_sort_keys(tmp, st, keys, ks.get(), n, bits);
 
     // ---- 4. runs ----
-    Scratch<unsigned> head(n + 1), pos(n + 1);
+    DevBuf<unsigned> head(n + 1), pos(n + 1);
     k_run_heads<<<grid_for(n + 1), 256, 0, st>>>(n, ks, head);
-    exclusive_sum(st, head, pos, n + 1);
-    unsigned h_runs = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_runs, pos + n, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    const i64 nruns = h_runs;
+    mv_exclusive_sum_u32(st, head, pos, n + 1);
+    const i64 nruns = read_back(pos + n, st);
     out->n = nruns;
-    HIP_CHECK(hipMalloc((void **)&out->d_key, 8 * nruns));
-    HIP_CHECK(hipMalloc((void **)&out->d_w, 8 * nruns));
-    Scratch<i64> run_start(nruns + 1);
+    out->d_key.reserve(nruns);
+    out->d_w.reserve(nruns);
+    DevBuf<i64> run_start(nruns + 1);
     k_run_fill<<<grid_for(n + 1), 256, 0, st>>>(n, ks, head, pos, run_start,
-                                                (u64 *)out->d_key);
+                                                (u64 *)out->d_key.get());
     if (!d_w) {
         k_run_lengths<<<grid_for(nruns), 256, 0, st>>>(nruns, run_start,
                                                        out->d_w);
         HIP_CHECK(hipStreamSynchronize(st));
     } else {
-        Scratch<i64> long_list(nruns);
-        Scratch<u64> long_count(1);
+        DevBuf<i64> long_list(nruns);
+        DevBuf<u64> long_count(1);
         HIP_CHECK(hipMemsetAsync(long_count, 0, 8, st));
         k_reduce_short<<<grid_for(nruns), 256, 0, st>>>(
             nruns, run_start, ws, out->d_w, long_list, long_count);
@@ -322,14 +251,6 @@ void mv_sort_reduce_keys(hipStream_t st, int64_t n, const uint64_t *d_keys_in,
             long_list, long_count, run_start, ws, out->d_w);
         HIP_CHECK(hipStreamSynchronize(st));
     }
-}
-
-void mv_coarse_dev_free(mv_coarse_dev *c) {
-    if (c->d_map) (void)hipFree(c->d_map);
-    if (c->d_xadj) (void)hipFree(c->d_xadj);
-    if (c->d_tails) (void)hipFree(c->d_tails);
-    if (c->d_w) (void)hipFree(c->d_w);
-    *c = mv_coarse_dev{};
 }
 
 int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
@@ -346,24 +267,20 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
     }
 
     // ---- 1. renumber ----
-    Scratch<unsigned> used(nv + 2), rank(nv + 1);
+    DevBuf<unsigned> used(nv + 2), rank(nv + 1);
     unsigned *err = used + nv + 1; // one word past the scan's closing 0
     HIP_CHECK(hipMemsetAsync(used, 0, 4 * (nv + 2), st));
     k_mark_labels<<<grid_for(nv), 256, 0, st>>>(nv, d_labels, used, err);
-    exclusive_sum(st, used, rank, nv + 1);
-    unsigned h_nc = 0, h_err = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_nc, rank + nv, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipMemcpyAsync(&h_err, err, 4, hipMemcpyDeviceToHost, st));
-    HIP_CHECK(hipStreamSynchronize(st));
-    if (h_err) {
+    mv_exclusive_sum_u32(st, used, rank, nv + 1);
+    const i64 nc = read_back(rank + nv, st);
+    if (read_back(err, st)) {
         std::fprintf(stderr,
                      "mv_coarsen: community label outside [0, nv=%lld)\n",
                      (long long)nv);
         return -1;
     }
-    const i64 nc = h_nc;
     out->nc = nc;
-    HIP_CHECK(hipMalloc((void **)&out->d_map, 8 * nv));
+    out->d_map.reserve(nv);
     k_gather_map<<<grid_for(nv), 256, 0, st>>>(nv, d_labels, rank,
                                                out->d_map);
     if (stop_if_identity && nc == nv) {
@@ -372,30 +289,27 @@ int mv_coarsen_device(hipStream_t st, int64_t nv, int64_t lne,
     }
 
     // ---- 2./3. keys + sort over the 2*shift live bits ----
-    int shift = 1;
-    while ((1ll << shift) < nc) shift++;
-    HIP_CHECK(hipMalloc((void **)&out->d_xadj, 8 * (nc + 1)));
+    const int shift = ceil_log2(nc);
+    out->d_xadj.reserve(nc + 1);
     if (lne == 0) {
         HIP_CHECK(hipMemsetAsync(out->d_xadj, 0, 8 * (nc + 1), st));
         HIP_CHECK(hipStreamSynchronize(st));
         return 0;
     }
-    Scratch<u64> keys(lne);
+    DevBuf<u64> keys(lne);
     k_coarse_keys<<<grid_for(lne), 256, 0, st>>>(nv, lne, d_xadj, d_tails,
                                                  out->d_map, shift, keys);
     mv_key_runs runs;
-    mv_sort_reduce_keys(st, lne, (const uint64_t *)keys.ptr, d_w, 2 * shift,
+    mv_sort_reduce_keys(st, lne, (const uint64_t *)keys.get(), d_w, 2 * shift,
                         &runs);
     const i64 nruns = runs.n;
     out->ne = nruns;
-    HIP_CHECK(hipMalloc((void **)&out->d_tails, 8 * std::max<i64>(nruns, 1)));
+    out->d_tails.reserve(nruns);
     k_coarse_rows<<<grid_for(std::max(nruns, nc + 1)), 256, 0, st>>>(
-        0, nc, nruns, shift, (const u64 *)runs.d_key, out->d_xadj,
+        0, nc, nruns, shift, (const u64 *)runs.d_key.get(), out->d_xadj,
         out->d_tails);
     HIP_CHECK(hipStreamSynchronize(st));
-    out->d_w = runs.d_w; // the run weights ARE the coarse weights
-    runs.d_w = nullptr;
-    mv_key_runs_free(&runs);
+    out->d_w = std::move(runs.d_w); // the run weights ARE the coarse weights
     return 0;
 }
 
@@ -436,8 +350,8 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
     for (i64 k = 0; k < lne && unit; k++) unit = w[k] == 1.0;
 
     hipStream_t st = nullptr; // the default stream: a one-shot entry
-    Scratch<i64> d_xadj(nv + 1), d_tails(lne), d_comm(nv);
-    Scratch<double> d_w(unit ? 0 : lne);
+    DevBuf<i64> d_xadj(nv + 1), d_tails(lne), d_comm(nv);
+    DevBuf<double> d_w(unit ? 0 : lne);
     HIP_CHECK(hipMemcpy(d_xadj, xadj, 8 * (nv + 1), hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_tails, tails, 8 * lne, hipMemcpyHostToDevice));
     HIP_CHECK(hipMemcpy(d_comm, comm, 8 * nv, hipMemcpyHostToDevice));
@@ -445,10 +359,8 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
 
     mv_coarse_dev c;
     if (mv_coarsen_device(st, nv, lne, d_xadj, d_tails,
-                          unit ? nullptr : d_w.ptr, d_comm, false, &c) != 0) {
-        mv_coarse_dev_free(&c);
+                          unit ? nullptr : d_w.get(), d_comm, false, &c) != 0)
         return nullptr;
-    }
     std::vector<i64> cx(c.nc + 1), ct(c.ne);
     std::vector<double> cw(c.ne);
     HIP_CHECK(hipMemcpy(map_out, c.d_map, 8 * nv, hipMemcpyDeviceToHost));
@@ -461,10 +373,8 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
                             hipMemcpyDeviceToHost));
     }
     const i64 parts[2] = {0, c.nc};
-    mv_graph *cg = mv_graph_from_csr(c.nc, 0, 1, parts, c.nc, c.ne, cx.data(),
-                                     ct.data(), cw.data());
-    mv_coarse_dev_free(&c);
-    return cg;
+    return mv_graph_from_csr(c.nc, 0, 1, parts, c.nc, c.ne, cx.data(),
+                             ct.data(), cw.data());
 }
 
 // ------------------------------------------------------------------------
@@ -472,31 +382,6 @@ extern "C" mv_graph *mv_coarsen_csr(int device, const mv_graph *g,
 // strings them together across the seam; DESIGN.md, multi-phase section).
 
 namespace {
-
-// first index in sorted[0,n) whose value is >= key
-__device__ __forceinline__ i64 lower_bound_u64(const u64 *__restrict__ a,
-                                               i64 n, u64 key) {
-    i64 lo = 0, hi = n;
-    while (lo < hi) {
-        const i64 mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
-__global__ void k_lower_bounds(const u64 *__restrict__ sorted, i64 n,
-                               const u64 *__restrict__ keys, int m,
-                               i64 *__restrict__ out) {
-    const int j = blockIdx.x * blockDim.x + threadIdx.x;
-    if (j < m) out[j] = lower_bound_u64(sorted, n, keys[j]);
-}
-
-__global__ void k_iota_u32(i64 n, unsigned *__restrict__ out) {
-    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
-         i += (i64)gridDim.x * blockDim.x)
-        out[i] = (unsigned)i;
-}
 
 // heads of the runs of equal sorted ids; head[n] = 0 closes the scan
 __global__ void k_id_heads(i64 n, const i64 *__restrict__ s,
@@ -605,43 +490,25 @@ __global__ __launch_bounds__(256) void k_coarse_keys_dist(
 
 } // namespace
 
-void mv_unique_ids_free(mv_unique_ids *u) {
-    if (u->d_uniq) (void)hipFree(u->d_uniq);
-    if (u->d_perm) (void)hipFree(u->d_perm);
-    if (u->d_run) (void)hipFree(u->d_run);
-    *u = mv_unique_ids{};
-}
-
 void mv_sort_unique_ids(hipStream_t st, int64_t n, const int64_t *d_ids,
                         int bits, mv_unique_ids *out) {
     *out = mv_unique_ids{};
     out->n = n;
-    HIP_CHECK(hipMalloc((void **)&out->d_uniq, 8 * std::max<i64>(n, 1)));
-    HIP_CHECK(hipMalloc((void **)&out->d_perm, 4 * std::max<i64>(n, 1)));
-    HIP_CHECK(hipMalloc((void **)&out->d_run, 4 * std::max<i64>(n, 1)));
+    out->d_uniq.reserve(n); // never null, n == 0 included
+    out->d_perm.reserve(n);
+    out->d_run.reserve(n);
     if (n == 0) return;
-    Scratch<i64> sorted(n);
-    Scratch<unsigned> iota(n), head(n + 1), pos(n + 1);
-    k_iota_u32<<<grid_for(n), 256, 0, st>>>(n, iota);
-    {
-        size_t bytes = 0;
-        (void)hipcub::DeviceRadixSort::SortPairs(
-            nullptr, bytes, d_ids, sorted.ptr, iota.ptr, out->d_perm, (int)n,
-            0, bits, st);
-        Scratch<char> tmp((i64)bytes);
-        HIP_CHECK(hipcub::DeviceRadixSort::SortPairs(
-            tmp.ptr, bytes, d_ids, sorted.ptr, iota.ptr, out->d_perm, (int)n,
-            0, bits, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
+    DevBuf<i64> sorted(n);
+    DevBuf<unsigned> iota(n), head(n + 1), pos(n + 1);
+    DevBuf<char> tmp; // freed at return, after the synchronising read
+    k_iota<<<grid_for(n), 256, 0, st>>>(n, iota.get());
+    cub_sort_pairs(tmp, st, d_ids, sorted.get(), iota.get(),
+                   out->d_perm.get(), n, bits);
     k_id_heads<<<grid_for(n + 1), 256, 0, st>>>(n, sorted, head);
-    exclusive_sum(st, head, pos, n + 1);
-    unsigned h_n = 0;
-    HIP_CHECK(hipMemcpyAsync(&h_n, pos + n, 4, hipMemcpyDeviceToHost, st));
+    mv_exclusive_sum_u32(st, head, pos, n + 1);
     k_id_runs<<<grid_for(n), 256, 0, st>>>(n, sorted, head, pos, out->d_run,
                                            out->d_uniq);
-    HIP_CHECK(hipStreamSynchronize(st));
-    out->nuniq = h_n;
+    out->nuniq = read_back(pos + n, st);
 }
 
 void mv_scatter_unique(hipStream_t st, const mv_unique_ids *u,
@@ -653,12 +520,11 @@ void mv_scatter_unique(hipStream_t st, const mv_unique_ids *u,
 
 void mv_lower_bounds(hipStream_t st, const uint64_t *d_sorted, int64_t n,
                      const uint64_t *h_keys, int m, int64_t *h_out) {
-    Scratch<u64> d_keys(m);
-    Scratch<i64> d_out(m);
+    DevBuf<uint64_t> d_keys(m);
+    DevBuf<i64> d_out(m);
     HIP_CHECK(hipMemcpyAsync(d_keys, h_keys, 8 * (size_t)m,
                              hipMemcpyHostToDevice, st));
-    k_lower_bounds<<<(m + 63) / 64, 64, 0, st>>>((const u64 *)d_sorted, n,
-                                                 d_keys, m, d_out);
+    lower_bounds_device(st, d_sorted, n, d_keys.get(), m, d_out.get());
     HIP_CHECK(hipMemcpyAsync(h_out, d_out, 8 * (size_t)m,
                              hipMemcpyDeviceToHost, st));
     HIP_CHECK(hipStreamSynchronize(st));
@@ -686,7 +552,9 @@ void mv_mark_owned(hipStream_t st, int64_t n, const int64_t *d_ids,
 
 void mv_exclusive_sum_u32(hipStream_t st, const unsigned *d_in,
                           unsigned *d_out, int64_t n) {
-    exclusive_sum(st, d_in, d_out, n);
+    DevBuf<char> tmp;
+    cub_exclusive_sum(tmp, st, d_in, d_out, n);
+    HIP_CHECK(hipStreamSynchronize(st)); // tmp dies with this scope
 }
 
 void mv_dense_ids(hipStream_t st, int64_t n, const unsigned *d_rank,

@@ -50,8 +50,7 @@
 #include <cstring>
 #include <vector>
 
-#include <hipcub/hipcub.hpp>
-
+#include "cub_util.h"
 #include "engine_internal.h"
 
 namespace {
@@ -121,14 +120,16 @@ __global__ void k3_init_comm(i64 lnv, i64 base,
     }
 }
 
-// ---- K10a: tag remote tails (exchangeVertexReqs, dspl.hpp:1140-1164) ----
-__global__ void k_select_remote(i64 lne, const i64 *__restrict__ tails,
+// ---- K10a: append the values outside [base, bound) to out: remote tails
+// (exchangeVertexReqs, dspl.hpp:1140-1164) and the candidate remote
+// communities of an iteration (dspl.hpp:670-700) ----
+__global__ void k_select_remote(i64 n, const i64 *__restrict__ vals,
                                 i64 base, i64 bound, i64 *__restrict__ out,
                                 unsigned long long *__restrict__ count) {
-    for (i64 e = blockIdx.x * (i64)blockDim.x + threadIdx.x; e < lne;
-         e += (i64)gridDim.x * blockDim.x) {
-        const i64 t = tails[e];
-        if (t < base || t >= bound) out[atomicAdd(count, 1ull)] = t;
+    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < n;
+         k += (i64)gridDim.x * blockDim.x) {
+        const i64 v = vals[k];
+        if (v < base || v >= bound) out[atomicAdd(count, 1ull)] = v;
     }
 }
 
@@ -141,12 +142,6 @@ __global__ void k_degrees(i64 lnv, const unsigned *__restrict__ sigma,
         const i64 v = sigma[k];
         deg[k] = (unsigned)(xadj[v + 1] - xadj[v]);
     }
-}
-
-__global__ void k_iota32(i64 n, unsigned *__restrict__ out) {
-    for (i64 i = blockIdx.x * (i64)blockDim.x + threadIdx.x; i < n;
-         i += (i64)gridDim.x * blockDim.x)
-        out[i] = (unsigned)i;
 }
 
 __global__ void k_invert_perm(i64 n, const unsigned *__restrict__ perm,
@@ -379,26 +374,6 @@ __global__ void k8_gather_comms(i64 n, const unsigned *__restrict__ svdata_int,
         out[k] = currComm[svdata_int[k]];
 }
 
-// ---- candidate remote communities (dspl.hpp:670-700) ----
-__global__ void k_filter_remote(i64 n, const i64 *__restrict__ vals,
-                                int shift, i64 base, i64 bound,
-                                i64 *__restrict__ out,
-                                unsigned long long *__restrict__ count) {
-    for (i64 k = blockIdx.x * (i64)blockDim.x + threadIdx.x; k < n;
-         k += (i64)gridDim.x * blockDim.x) {
-        const i64 c = vals[k] >> shift; // label
-        if (c < base || c >= bound) out[atomicAdd(count, 1ull)] = c;
-    }
-}
-
-// per-owner boundaries of a sorted id array (one thread per rank)
-__global__ void k_owner_bounds(const i64 *__restrict__ sorted, i64 n,
-                               const i64 *__restrict__ parts, int nranks,
-                               i64 *__restrict__ bounds) {
-    int r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r <= nranks) bounds[r] = dev_lower_bound(sorted, n, parts[r]);
-}
-
 // ---- K9: cinfo reply gather (dspl.hpp:776-929) ----
 __global__ void k9_reply_info(i64 n, const i64 *__restrict__ req_ids, i64 base,
                               const unsigned *__restrict__ sigma_inv,
@@ -518,10 +493,21 @@ __global__ void k_depermute32(i64 lnv, const unsigned *__restrict__ sigma,
 
 } // namespace
 
-void select_remote(hipStream_t st, i64 lne, const i64 *d_tails, i64 base,
-                   i64 bound, i64 *d_out, unsigned long long *d_count) {
-    k_select_remote<<<grid_for(lne), 256, 0, st>>>(lne, d_tails, base, bound,
-                                                   d_out, d_count);
+i64 remote_ids(hipStream_t st, i64 n, const i64 *d_vals, i64 base, i64 bound,
+               int bits, DevBuf<i64> &d_ids) {
+    DevBuf<i64> d_rem(n), d_sorted; // temporaries: freed at return
+    DevBuf<unsigned long long> d_count(1);
+    DevBuf<char> d_tmp;
+    HIP_CHECK(hipMemsetAsync(d_count, 0, 8, st));
+    k_select_remote<<<grid_for(n), 256, 0, st>>>(n, d_vals, base, bound, d_rem,
+                                                 d_count);
+    const i64 nrem = (i64)read_back(d_count.get(), st);
+    d_sorted.reserve(nrem);
+    d_ids.reserve(nrem);
+    cub_sort_keys(d_tmp, st, d_rem.get(), d_sorted.get(), nrem, bits);
+    i64 *d_n = (i64 *)d_count.get(); // reuse as output slot
+    cub_unique(d_tmp, st, d_sorted.get(), d_ids.get(), d_n, nrem);
+    return read_back(d_n, st);
 }
 
 static void build_sell(mv_engine *e);
@@ -702,8 +688,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     }
     e->lnv = mv_graph_lnv(g);
     e->lne = mv_graph_lne(g);
-    e->sort_bits = 1;
-    while ((1ll << e->sort_bits) < e->nv) e->sort_bits++;
+    e->sort_bits = ceil_log2(e->nv);
     e->parts_h.assign(mv_graph_parts(g), mv_graph_parts(g) + e->nranks + 1);
     e->base = e->parts_h[e->rank];
     e->bound = e->parts_h[e->rank + 1];
@@ -768,7 +753,7 @@ int mv_engine_load_graph(mv_engine *e, const mv_graph *g) {
     } else if (hint) {
         HIP_CHECK(hipMemcpy(e->d_sigma, hint, 4 * lnv, hipMemcpyHostToDevice));
     } else {
-        k_iota32<<<grid_for(lnv), 256>>>(lnv, e->d_sigma);
+        k_iota<<<grid_for(lnv), 256>>>(lnv, e->d_sigma.get());
     }
     k_invert_perm<<<grid_for(lnv), 256>>>(lnv, e->d_sigma, e->d_sigma_inv);
 
@@ -1026,6 +1011,203 @@ void comm_allreduce_host(mv_engine *e, double *vals, int n) {
     HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 
+// ---- build_sell, step by step. Every step works on e->stream; d_tmp is
+// the hipCUB temporary they share. ----
+
+// 1. Degree order. perm = identity with a spatial hint (sigma carries the
+// order), degree-descending otherwise (load balance for skewed degree
+// distributions); then d_sdeg holds the sorted degrees, else it stays null.
+// Reads lnv, d_sigma, d_xadj, has_hint, skewed; sets d_deg, d_perm, d_iota,
+// perm_identity.
+static void sell_degree_order(mv_engine *e, DevBuf<char> &d_tmp,
+                              DevBuf<unsigned> &d_sdeg) {
+    hipStream_t st = e->stream;
+    const i64 lnv = e->lnv;
+    k_degrees<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_sigma, e->d_xadj,
+                                             e->d_deg);
+    e->perm_identity = e->has_hint && !e->skewed; // until step 3 permutes it
+    if (e->perm_identity) {
+        k_iota<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm.get());
+        return;
+    }
+    k_iota<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_iota.get());
+    d_sdeg.reserve(lnv);
+    cub_sort_pairs_descending(d_tmp, st, e->d_deg.get(), d_sdeg.get(),
+                              e->d_iota.get(), e->d_perm.get(), lnv, 32);
+}
+
+// 2. High-degree split + per-vertex hash regions of a degree-sorted order
+// (unit: wave-per-vertex atomic hash; -w: per-lane serial hash in edge
+// order). Reads lnv, lne, skewed, unit_weights, d_tails, base, bound,
+// d_sigma_inv, d_ghosts, nghost; sets nhi, nlh, and for nlh > 0 d_tidx32,
+// d_hash_off, hash_hub_elems, hash_total, d_hkeys, d_hacc, d_lh_list.
+static void sell_hash_bands(mv_engine *e, const DevBuf<unsigned> &d_sdeg) {
+    hipStream_t st = e->stream;
+    const i64 lnv = e->lnv;
+    e->nhi = 0;
+    e->nlh = 0;
+    if (!d_sdeg) return; // identity order: never skewed
+    std::vector<unsigned> sdeg(lnv);
+    if (lnv) // a rank may own no vertices (null data())
+        HIP_CHECK(hipMemcpyAsync(sdeg.data(), d_sdeg, 4 * lnv,
+                                 hipMemcpyDeviceToHost, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    // MV_HI_THRESH (perf only): degree bound above which a vertex
+    // takes the hub path (wave hash for unit, per-lane hash for -w)
+    // instead of the LDS-slot + linear-spill lane path
+    static const unsigned HI_THRESH = [] {
+        const char *s = getenv("MV_HI_THRESH");
+        return s ? (unsigned)atoi(s) : 256u;
+    }();
+    // MV_LH_THRESH: degree bound above which a vertex takes the
+    // per-lane hash band (below: LDS slots + linear spill). Default ==
+    // HI_THRESH: the band only covers WEIGHTED hubs (where it replaces
+    // the old cap-scanning kernel); extending it to the unit 24-256
+    // band was measured SLOWER than 24 LDS slots + linear spill on the
+    // dense social shape (11.3 -> 8.3 G, experiments/RESULTS.md) — L2
+    // hash probes lose to LDS at ~25 candidates.
+    static const unsigned LH_THRESH = [] {
+        const char *s = getenv("MV_LH_THRESH");
+        return s ? (unsigned)atoi(s) : 256u;
+    }();
+    i64 nhi = 0;
+    while (nhi < lnv && sdeg[nhi] > HI_THRESH) nhi++;
+    i64 nlh = 0;
+    while (nlh < lnv && sdeg[nlh] > LH_THRESH) nlh++;
+    e->nhi = (e->skewed && e->unit_weights) ? nhi : 0;
+    e->nlh = e->skewed ? std::max<i64>(nlh, e->nhi) : 0;
+    if (e->nlh == 0) return;
+    e->d_tidx32.reserve(e->lne);
+    k_translate_tails<<<grid_for(e->lne), 256, 0, st>>>(
+        e->lne, e->d_tails, e->base, e->bound, e->d_sigma_inv, e->d_ghosts,
+        e->nghost, lnv, e->d_tidx32);
+    std::vector<i64> hoff(e->nlh + 1);
+    i64 acc = 0;
+    for (i64 t = 0; t < e->nlh; t++) {
+        hoff[t] = acc;
+        i64 cap = 64;
+        while (cap < 2 * (i64)sdeg[t]) cap <<= 1;
+        acc += cap;
+    }
+    hoff[e->nlh] = acc;
+    e->hash_hub_elems = e->nhi > 0 ? hoff[e->nhi] : 0;
+    e->d_hash_off.reserve(e->nlh + 1);
+    HIP_CHECK(hipMemcpyAsync(e->d_hash_off, hoff.data(), 8 * (e->nlh + 1),
+                             hipMemcpyHostToDevice, st));
+    e->hash_total = acc;
+    if (e->d_hkeys.reserve(acc)) { // the three grow together
+        e->d_hacc.reserve(acc);
+        e->d_lh_list.reserve(acc / 2 + 1);
+    }
+    HIP_CHECK(hipStreamSynchronize(st));
+}
+
+// 3. Exports-first SELL order (halo overlap): positions [0, nexp) hold
+// the vertices some peer wants (the svdata set), so the sweep can run
+// them as a first launch and halo #1a for the NEXT iteration — which
+// only needs their targets — can overlap the interior sweep + the
+// whole epilogue on stream2/comm2 (north_star: "#1a overlapped with
+// the local sweep on a second HIP stream"). Stable partition: locality
+// inside each group is preserved. Pure layout, results identical.
+// Reads lnv, nranks, skewed, ssz, d_svdata_int, comm2 / lb; sets nexp,
+// overlap, and when it partitions d_perm, perm_identity.
+static void sell_exports_first(mv_engine *e, DevBuf<char> &d_tmp) {
+    hipStream_t st = e->stream;
+    const i64 lnv = e->lnv;
+    e->nexp = 0;
+    e->overlap = 0;
+    if (e->nranks == 1 || e->skewed || e->ssz == 0 || !has_second_channel(e) ||
+        getenv("MV_NO_OVERLAP"))
+        return;
+    // device-side stable partition (two hipCUB Flagged selects): the
+    // host round trip cost ~ms per run at 8-GPU sizes
+    DevBuf<unsigned char> d_mark(lnv), d_flags(lnv); // freed at return
+    DevBuf<unsigned> d_out(lnv);
+    DevBuf<i64> d_num(1);
+    HIP_CHECK(hipMemsetAsync(d_mark, 0, lnv, st));
+    k_scatter_mark<<<grid_for(e->ssz), 256, 0, st>>>(e->ssz, e->d_svdata_int,
+                                                     d_mark);
+    k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
+                                                  d_flags, 0);
+    cub_select_flagged(d_tmp, st, e->d_perm.get(), d_flags.get(), d_out.get(),
+                       d_num.get(), lnv);
+    e->nexp = read_back(d_num.get(), st);
+    k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
+                                                  d_flags, 1);
+    cub_select_flagged(d_tmp, st, e->d_perm.get(), d_flags.get(),
+                       d_out + e->nexp, d_num.get(), lnv);
+    HIP_CHECK(hipMemcpyAsync(e->d_perm, d_out, 4 * lnv,
+                             hipMemcpyDeviceToDevice, st));
+    HIP_CHECK(hipStreamSynchronize(st));
+    e->overlap = 1;
+    e->perm_identity = 0;
+}
+
+// 4. The SELL image over d_perm: slice offsets, tails translated inline,
+// and for unit graphs the row sort. Reads lnv, nchunks, d_perm, d_deg,
+// d_sigma, d_sigma_inv, d_xadj, d_tails, d_ew, base, bound, d_ghosts,
+// nghost, unit_weights, skewed; sets d_chunk_off, sell_entries,
+// d_sell_tidx, d_sell_w, sell_sorted.
+static void sell_fill_image(mv_engine *e, DevBuf<char> &d_tmp) {
+    hipStream_t st = e->stream;
+    const i64 lnv = e->lnv;
+    DevBuf<i64> d_sizes(e->nchunks); // freed at return
+    k_chunk_sizes<<<grid_for(e->nchunks), 256, 0, st>>>(
+        e->nchunks, lnv, e->d_perm, e->d_deg, d_sizes);
+    HIP_CHECK(hipMemsetAsync(e->d_chunk_off, 0, 8, st));
+    cub_inclusive_sum(d_tmp, st, d_sizes.get(), e->d_chunk_off + 1,
+                      e->nchunks);
+    const i64 total = read_back(e->d_chunk_off + e->nchunks, st);
+    e->sell_entries = total;
+    e->d_sell_tidx.reserve(total);
+    if (!e->unit_weights) e->d_sell_w.reserve(total);
+    k_fill_sell<<<grid_for(lnv), 256, 0, st>>>(
+        lnv, e->d_perm, e->d_sigma, e->d_sigma_inv, e->d_xadj, e->d_tails,
+        e->d_ew, e->base, e->bound, e->d_ghosts, e->nghost, e->d_chunk_off,
+        e->d_sell_tidx, e->unit_weights ? nullptr : e->d_sell_w.get());
+    // unit graphs: re-sort rows by internal index for gather locality
+    // (see k_sell_sort_rows; results identical, measured +4-5%)
+    e->sell_sorted = 0;
+    if (e->unit_weights && !e->skewed && !getenv("MV_NO_ROWSORT")) {
+        k_sell_sort_rows<<<grid_for(lnv), 256, 0, st>>>(
+            lnv, e->d_perm, e->d_deg, e->d_chunk_off, e->d_sell_tidx);
+        e->sell_sorted = 1;
+    }
+}
+
+// 5. Per-thread spill extents of K4. Reads lnv, sweep_grid, skewed,
+// max_degree, nlh, d_perm, d_deg; sets d_spill_off, d_spill_k, d_spill_a.
+static void sell_spill_extents(mv_engine *e) {
+    hipStream_t st = e->stream;
+    const i64 nthreads = (i64)e->sweep_grid * 256;
+    i64 total;
+    if (!e->skewed) {
+        const i64 per = std::max<i64>(e->max_degree, 1);
+        k_spill_uniform<<<grid_for(nthreads), 256, 0, st>>>(nthreads, per,
+                                                            e->d_spill_off);
+        total = nthreads * per;
+    } else {
+        DevBuf<i64> d_need(nthreads); // freed with this block
+        k_spill_need<<<grid_for(nthreads), 256, 0, st>>>(
+            nthreads, e->nlh, e->lnv, e->d_perm, e->d_deg, 4, d_need);
+        std::vector<i64> need(nthreads), off(nthreads);
+        HIP_CHECK(hipMemcpyAsync(need.data(), d_need, 8 * nthreads,
+                                 hipMemcpyDeviceToHost, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+        i64 acc = 0;
+        for (i64 t = 0; t < nthreads; t++) {
+            off[t] = acc;
+            acc += need[t];
+        }
+        total = acc;
+        HIP_CHECK(hipMemcpyAsync(e->d_spill_off, off.data(), 8 * nthreads,
+                                 hipMemcpyHostToDevice, st));
+        HIP_CHECK(hipStreamSynchronize(st));
+    }
+    e->d_spill_k.reserve(total);
+    e->d_spill_a.reserve(total);
+}
+
 // Build the SELL image, internal order, spill extents and the high-degree
 // hash regions. Pure graph-layout preparation (a function of the static
 // graph + the ghost list), analogous to the reference's CSR existing
@@ -1033,212 +1215,14 @@ void comm_allreduce_host(mv_engine *e, double *vals, int n) {
 // after ghost discovery inside the span for multi-rank ones (the ghost
 // slots feed the tail translation).
 static void build_sell(mv_engine *e) {
-    hipStream_t st = e->stream;
-    const i64 lnv = e->lnv;
-    // build the SELL image over the internal order (tails translated
-    // inline). perm = identity with a spatial hint, degree-sorted
-    // otherwise (load balance for skewed degree distributions).
-    k_degrees<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_sigma, e->d_xadj,
-                                             e->d_deg);
-    e->nhi = 0; // set by the skewed branch below when applicable
-    e->nlh = 0;
-    e->perm_identity = 0;
-    if (e->has_hint && !e->skewed) {
-        k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm);
-        e->perm_identity = 1; // until something below permutes it
-    } else {
-        k_iota32<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_iota);
-        DevBuf<unsigned> d_degs; // temporaries: freed with this block
-        DevBuf<char> d_tmp;
-        d_degs.reserve(lnv);
-        size_t tb = 0;
-        (void)hipcub::DeviceRadixSort::SortPairsDescending(
-            nullptr, tb, e->d_deg.get(), d_degs.get(), e->d_iota.get(),
-            e->d_perm.get(), lnv, 0, 32, st);
-        d_tmp.reserve(tb);
-        (void)hipcub::DeviceRadixSort::SortPairsDescending(
-            d_tmp.get(), tb, e->d_deg.get(), d_degs.get(), e->d_iota.get(),
-            e->d_perm.get(), lnv, 0, 32, st);
-        // high-degree split + per-vertex hash regions (unit: wave-per-
-        // vertex atomic hash; -w: per-lane serial hash in edge order)
-        std::vector<unsigned> sdeg(lnv);
-        if (lnv) // a rank may own no vertices (null data())
-            HIP_CHECK(hipMemcpyAsync(sdeg.data(), d_degs, 4 * lnv,
-                                     hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        // MV_HI_THRESH (perf only): degree bound above which a vertex
-        // takes the hub path (wave hash for unit, per-lane hash for -w)
-        // instead of the LDS-slot + linear-spill lane path
-        static const unsigned HI_THRESH = [] {
-            const char *s = getenv("MV_HI_THRESH");
-            return s ? (unsigned)atoi(s) : 256u;
-        }();
-        // MV_LH_THRESH: degree bound above which a vertex takes the
-        // per-lane hash band (below: LDS slots + linear spill). Default ==
-        // HI_THRESH: the band only covers WEIGHTED hubs (where it replaces
-        // the old cap-scanning kernel); extending it to the unit 24-256
-        // band was measured SLOWER than 24 LDS slots + linear spill on the
-        // dense social shape (11.3 -> 8.3 G, experiments/RESULTS.md) — L2
-        // hash probes lose to LDS at ~25 candidates.
-        static const unsigned LH_THRESH = [] {
-            const char *s = getenv("MV_LH_THRESH");
-            return s ? (unsigned)atoi(s) : 256u;
-        }();
-        i64 nhi = 0;
-        while (nhi < lnv && sdeg[nhi] > HI_THRESH) nhi++;
-        i64 nlh = 0;
-        while (nlh < lnv && sdeg[nlh] > LH_THRESH) nlh++;
-        e->nhi = (e->skewed && e->unit_weights) ? nhi : 0;
-        e->nlh = e->skewed ? std::max<i64>(nlh, e->nhi) : 0;
-        if (e->nlh > 0) {
-            e->d_tidx32.reserve(e->lne);
-            k_translate_tails<<<grid_for(e->lne), 256, 0, st>>>(
-                e->lne, e->d_tails, e->base, e->bound, e->d_sigma_inv,
-                e->d_ghosts, e->nghost, lnv, e->d_tidx32);
-            std::vector<i64> hoff(e->nlh + 1);
-            i64 acc = 0;
-            for (i64 t = 0; t < e->nlh; t++) {
-                hoff[t] = acc;
-                i64 cap = 64;
-                while (cap < 2 * (i64)sdeg[t]) cap <<= 1;
-                acc += cap;
-            }
-            hoff[e->nlh] = acc;
-            e->hash_hub_elems = e->nhi > 0 ? hoff[e->nhi] : 0;
-            e->d_hash_off.reserve(e->nlh + 1);
-            HIP_CHECK(hipMemcpyAsync(e->d_hash_off, hoff.data(),
-                                     8 * (e->nlh + 1),
-                                     hipMemcpyHostToDevice, st));
-            e->hash_total = acc;
-            if (e->d_hkeys.reserve(acc)) { // the three grow together
-                e->d_hacc.reserve(acc);
-                e->d_lh_list.reserve(acc / 2 + 1);
-            }
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-    }
-
-    // Exports-first SELL order (halo overlap): positions [0, nexp) hold
-    // the vertices some peer wants (the svdata set), so the sweep can run
-    // them as a first launch and halo #1a for the NEXT iteration — which
-    // only needs their targets — can overlap the interior sweep + the
-    // whole epilogue on stream2/comm2 (north_star: "#1a overlapped with
-    // the local sweep on a second HIP stream"). Stable partition: locality
-    // inside each group is preserved. Pure layout, results identical.
-    e->nexp = 0;
-    e->overlap = 0;
-    if (e->nranks > 1 && !e->skewed && e->ssz > 0 && has_second_channel(e) &&
-        !getenv("MV_NO_OVERLAP")) {
-        // device-side stable partition (two hipCUB Flagged selects): the
-        // host round trip cost ~ms per run at 8-GPU sizes
-        DevBuf<unsigned char> d_mark, d_flags; // freed with this block
-        DevBuf<unsigned> d_out;
-        DevBuf<i64> d_num;
-        DevBuf<char> d_tsel;
-        d_mark.reserve(lnv);
-        d_flags.reserve(lnv);
-        d_out.reserve(lnv);
-        d_num.reserve(1);
-        HIP_CHECK(hipMemsetAsync(d_mark, 0, lnv, st));
-        k_scatter_mark<<<grid_for(e->ssz), 256, 0, st>>>(
-            e->ssz, e->d_svdata_int, d_mark);
-        k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
-                                                      d_flags, 0);
-        size_t tsel = 0;
-        (void)hipcub::DeviceSelect::Flagged(nullptr, tsel, e->d_perm.get(),
-                                            d_flags.get(), d_out.get(),
-                                            d_num.get(), lnv, st);
-        d_tsel.reserve(tsel);
-        (void)hipcub::DeviceSelect::Flagged(d_tsel.get(), tsel,
-                                            e->d_perm.get(), d_flags.get(),
-                                            d_out.get(), d_num.get(), lnv, st);
-        HIP_CHECK(hipMemcpyAsync(&e->nexp, d_num, 8, hipMemcpyDeviceToHost,
-                                 st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        k_gather_flags<<<grid_for(lnv), 256, 0, st>>>(lnv, e->d_perm, d_mark,
-                                                      d_flags, 1);
-        (void)hipcub::DeviceSelect::Flagged(d_tsel.get(), tsel,
-                                            e->d_perm.get(), d_flags.get(),
-                                            d_out + e->nexp, d_num.get(), lnv,
-                                            st);
-        HIP_CHECK(hipMemcpyAsync(e->d_perm, d_out, 4 * lnv,
-                                 hipMemcpyDeviceToDevice, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        e->overlap = 1;
-        e->perm_identity = 0;
-    }
-
-    {
-        DevBuf<i64> d_sizes; // freed with this block
-        DevBuf<char> d_tmp2;
-        d_sizes.reserve(e->nchunks);
-        k_chunk_sizes<<<grid_for(e->nchunks), 256, 0, st>>>(
-            e->nchunks, lnv, e->d_perm, e->d_deg, d_sizes);
-        HIP_CHECK(hipMemsetAsync(e->d_chunk_off, 0, 8, st));
-        size_t tb2 = 0;
-        (void)hipcub::DeviceScan::InclusiveSum(nullptr, tb2, d_sizes.get(),
-                                         e->d_chunk_off + 1, e->nchunks,
-                                         st);
-        d_tmp2.reserve(tb2);
-        (void)hipcub::DeviceScan::InclusiveSum(d_tmp2.get(), tb2,
-                                         d_sizes.get(), e->d_chunk_off + 1,
-                                         e->nchunks, st);
-        i64 total = 0;
-        HIP_CHECK(hipMemcpyAsync(&total, e->d_chunk_off + e->nchunks, 8,
-                                 hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        e->sell_entries = total;
-        e->d_sell_tidx.reserve(total);
-        if (!e->unit_weights) e->d_sell_w.reserve(total);
-        k_fill_sell<<<grid_for(lnv), 256, 0, st>>>(
-            lnv, e->d_perm, e->d_sigma, e->d_sigma_inv, e->d_xadj,
-            e->d_tails, e->d_ew, e->base, e->bound, e->d_ghosts, e->nghost,
-            e->d_chunk_off, e->d_sell_tidx,
-            e->unit_weights ? nullptr : e->d_sell_w.get());
-        // unit graphs: re-sort rows by internal index for gather locality
-        // (see k_sell_sort_rows; results identical, measured +4-5%)
-        e->sell_sorted = 0;
-        if (e->unit_weights && !e->skewed && !getenv("MV_NO_ROWSORT")) {
-            k_sell_sort_rows<<<grid_for(lnv), 256, 0, st>>>(
-                lnv, e->d_perm, e->d_deg, e->d_chunk_off, e->d_sell_tidx);
-            e->sell_sorted = 1;
-        }
-    }
-
-    // per-thread spill extents
-    {
-        const i64 nthreads = (i64)e->sweep_grid * 256;
-        i64 total;
-        if (!e->skewed) {
-            const i64 per = std::max<i64>(e->max_degree, 1);
-            k_spill_uniform<<<grid_for(nthreads), 256, 0, st>>>(
-                nthreads, per, e->d_spill_off);
-            total = nthreads * per;
-        } else {
-            DevBuf<i64> d_need; // freed with this block
-            d_need.reserve(nthreads);
-            k_spill_need<<<grid_for(nthreads), 256, 0, st>>>(
-                nthreads, e->nlh, lnv, e->d_perm, e->d_deg, 4, d_need);
-            std::vector<i64> need(nthreads), off(nthreads);
-            HIP_CHECK(hipMemcpyAsync(need.data(), d_need, 8 * nthreads,
-                                     hipMemcpyDeviceToHost, st));
-            HIP_CHECK(hipStreamSynchronize(st));
-            i64 acc = 0;
-            for (i64 t = 0; t < nthreads; t++) {
-                off[t] = acc;
-                acc += need[t];
-            }
-            total = acc;
-            HIP_CHECK(hipMemcpyAsync(e->d_spill_off, off.data(),
-                                     8 * nthreads, hipMemcpyHostToDevice,
-                                     st));
-            HIP_CHECK(hipStreamSynchronize(st));
-        }
-        e->d_spill_k.reserve(total);
-        e->d_spill_a.reserve(total);
-    }
-
-    HIP_CHECK(hipStreamSynchronize(st));
+    DevBuf<char> d_tmp;      // temporaries: freed at return, after the
+    DevBuf<unsigned> d_sdeg; // stream has drained
+    sell_degree_order(e, d_tmp, d_sdeg);
+    sell_hash_bands(e, d_sdeg);
+    sell_exports_first(e, d_tmp);
+    sell_fill_image(e, d_tmp);
+    sell_spill_extents(e);
+    HIP_CHECK(hipStreamSynchronize(e->stream));
 }
 
 // Halo #1a (dspl.hpp:583-647) on (comm, stream): gather the exports'
@@ -1349,45 +1333,30 @@ static void halo_prep(mv_engine *e, const i64 *curr,
         e->d_rc_ids.reserve(cand_max);
         e->d_rc_info.reserve(cand_max);
         e->d_rcu.reserve(cand_max);
-        size_t t1 = 0, t2 = 0;
-        (void)hipcub::DeviceRadixSort::SortKeys(
-            nullptr, t1, e->d_cand.get(), e->d_cand_sorted.get(), cand_max, 0,
-            e->sort_bits, st2);
-        i64 *dummy = nullptr;
-        (void)hipcub::DeviceSelect::Unique(nullptr, t2,
-                                           e->d_cand_sorted.get(),
-                                           e->d_rc_ids.get(), dummy, cand_max,
-                                           st2);
-        e->d_cub_tmp.reserve((i64)std::max(t1, t2));
+        // the sort + unique below never have more than cand_max ids: sized
+        // here, d_cub_tmp does not grow (a hipFree would device-sync and
+        // re-serialize the overlapped pipeline) before the next load
+        cub_presize_sort_unique(e->d_cub_tmp, cand_max, e->sort_bits);
     }
+    // two sources, ghost labels then curr, into one candidate array
     HIP_CHECK(hipMemsetAsync(e->d_count, 0, 8, st2));
-    k_filter_remote<<<grid_for(std::max<i64>(e->nghost, 1)), 256, 0, st2>>>(
-        e->nghost, e->d_ghost_labels, /*shift*/ 0, e->base, e->bound,
-        e->d_cand, e->d_count);
-    k_filter_remote<<<grid_for(lnv), 256, 0, st2>>>(
-        lnv, curr, /*shift*/ 0, e->base, e->bound, e->d_cand, e->d_count);
-    unsigned long long ncand = 0;
-    HIP_CHECK(hipMemcpyAsync(&ncand, e->d_count, 8, hipMemcpyDeviceToHost,
-                             st2));
-    HIP_CHECK(hipStreamSynchronize(st2));
-    size_t tb = (size_t)e->d_cub_tmp.cap;
-    (void)hipcub::DeviceRadixSort::SortKeys(
-        e->d_cub_tmp.get(), tb, e->d_cand.get(), e->d_cand_sorted.get(),
-        (int64_t)ncand, 0, e->sort_bits, st2);
+    k_select_remote<<<grid_for(std::max<i64>(e->nghost, 1)), 256, 0, st2>>>(
+        e->nghost, e->d_ghost_labels, e->base, e->bound, e->d_cand,
+        e->d_count);
+    k_select_remote<<<grid_for(lnv), 256, 0, st2>>>(
+        lnv, curr, e->base, e->bound, e->d_cand, e->d_count);
+    const i64 ncand = (i64)read_back(e->d_count.get(), st2);
+    cub_sort_keys(e->d_cub_tmp, st2, e->d_cand.get(), e->d_cand_sorted.get(),
+                  ncand, e->sort_bits);
     i64 *d_nrc = (i64 *)e->d_count.get(); // reuse as output slot
-    tb = (size_t)e->d_cub_tmp.cap;
-    (void)hipcub::DeviceSelect::Unique(e->d_cub_tmp.get(), tb,
-                                       e->d_cand_sorted.get(),
-                                       e->d_rc_ids.get(), d_nrc,
-                                       (int64_t)ncand, st2);
-    i64 nrc = 0;
-    HIP_CHECK(hipMemcpyAsync(&nrc, d_nrc, 8, hipMemcpyDeviceToHost, st2));
-    HIP_CHECK(hipStreamSynchronize(st2));
+    cub_unique(e->d_cub_tmp, st2, e->d_cand_sorted.get(), e->d_rc_ids.get(),
+               d_nrc, ncand);
+    const i64 nrc = read_back(d_nrc, st2);
 
     // ---- halo #1b/#1c/#1d: request (size,degree) of those communities
     // from their owners (dspl.hpp:719-929) ----
-    k_owner_bounds<<<1, p + 1, 0, st2>>>(e->d_rc_ids, nrc, e->d_parts, p,
-                                         e->d_bounds);
+    lower_bounds_device(st2, e->d_rc_ids.get(), nrc, e->d_parts.get(), p + 1,
+                        e->d_bounds.get());
     rc_bounds.assign(p + 1, 0);
     HIP_CHECK(hipMemcpyAsync(rc_bounds.data(), e->d_bounds, 8 * (p + 1),
                              hipMemcpyDeviceToHost, st2));
@@ -1396,10 +1365,7 @@ static void halo_prep(mv_engine *e, const i64 *curr,
     for (int r = 0; r < p; r++) reqs[r] = rc_bounds[r + 1] - rc_bounds[r];
     allgather_counts(e, reqs.data(), /*on_device*/ false, matrix.data(), comm,
                      st2);
-    req_off.assign(p + 1, 0);
-    for (int r = 0; r < p; r++)
-        req_off[r + 1] =
-            req_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
+    recv_offsets(matrix, p, me, /*with_own*/ false, req_off);
     const i64 nreq = req_off[p];
     e->halo.prep_calls++;
     e->halo.nrc_sum += nrc;
@@ -1440,48 +1406,18 @@ static void exchange_vertex_reqs(mv_engine *e) {
     hipStream_t st = e->stream;
     const i64 lnv = e->lnv, lne = e->lne;
     const int p = e->nranks, me = e->rank;
-    HIP_CHECK(hipMemsetAsync(e->d_count, 0, 8, st));
     if (p == 1) {
         e->nghost = 0;
         e->ssz = 0;
         return; // the SELL image was built at load
     }
-    {
-        DevBuf<i64> d_rem, d_sorted, d_ng; // temporaries: freed with this
-        DevBuf<char> d_tmp;                // block
-        d_rem.reserve(lne);
-        select_remote(st, lne, e->d_tails, e->base, e->bound, d_rem,
-                      e->d_count);
-        unsigned long long nrem = 0;
-        HIP_CHECK(hipMemcpyAsync(&nrem, e->d_count, 8, hipMemcpyDeviceToHost,
-                                 st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        // sort + unique -> ghosts
-        d_sorted.reserve((i64)nrem);
-        e->d_ghosts.reserve((i64)nrem);
-        d_ng.reserve(1);
-        size_t tmp1 = 0, tmp2 = 0;
-        (void)hipcub::DeviceRadixSort::SortKeys(
-            nullptr, tmp1, d_rem.get(), d_sorted.get(), (int64_t)nrem, 0,
-            e->sort_bits, st);
-        (void)hipcub::DeviceSelect::Unique(nullptr, tmp2, d_sorted.get(),
-                                           e->d_ghosts.get(), d_ng.get(),
-                                           (int64_t)nrem, st);
-        d_tmp.reserve((i64)std::max(tmp1, tmp2));
-        (void)hipcub::DeviceRadixSort::SortKeys(
-            d_tmp.get(), tmp1, d_rem.get(), d_sorted.get(), (int64_t)nrem, 0,
-            e->sort_bits, st);
-        (void)hipcub::DeviceSelect::Unique(d_tmp.get(), tmp2, d_sorted.get(),
-                                           e->d_ghosts.get(), d_ng.get(),
-                                           (int64_t)nrem, st);
-        HIP_CHECK(hipMemcpyAsync(&e->nghost, d_ng, 8, hipMemcpyDeviceToHost,
-                                 st));
-        HIP_CHECK(hipStreamSynchronize(st));
-    }
+    // ghosts: the sorted distinct remote tails
+    e->nghost = remote_ids(st, lne, e->d_tails, e->base, e->bound,
+                           e->sort_bits, e->d_ghosts);
 
     // per-owner segments of my (sorted) want list
-    k_owner_bounds<<<1, p + 1, 0, st>>>(e->d_ghosts, e->nghost, e->d_parts, p,
-                                        e->d_bounds);
+    lower_bounds_device(st, e->d_ghosts.get(), e->nghost, e->d_parts.get(),
+                        p + 1, e->d_bounds.get());
     e->recv_off.resize(p + 1);
     HIP_CHECK(hipMemcpyAsync(e->recv_off.data(), e->d_bounds, 8 * (p + 1),
                              hipMemcpyDeviceToHost, st));
@@ -1492,10 +1428,7 @@ static void exchange_vertex_reqs(mv_engine *e) {
     for (int r = 0; r < p; r++) want[r] = e->recv_off[r + 1] - e->recv_off[r];
     allgather_counts(e, want.data(), /*on_device*/ false, matrix.data(),
                      e->comm, st);
-    e->send_off.assign(p + 1, 0);
-    for (int r = 0; r < p; r++)
-        e->send_off[r + 1] =
-            e->send_off[r] + ((r == me) ? 0 : matrix[(size_t)r * p + me]);
+    recv_offsets(matrix, p, me, /*with_own*/ false, e->send_off);
     e->ssz = e->send_off[p];
     e->d_svdata.reserve(e->ssz);
     e->d_svdata_int.reserve(e->ssz);

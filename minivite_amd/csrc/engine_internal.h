@@ -7,33 +7,25 @@
 //   sweep.hip       the K4 sweep kernels and their launch dispatch (sweep_*)
 //   multiphase.hip  the distributed aggregation over the transport seam and
 //                   the one multi-phase driver (mv_hierarchy)
-//   coarsen.hip     the transport-free aggregation kernels (coarsen.h)
+//   coarsen.hip     the transport-free aggregation kernels (coarsen.h);
+//                   includes neither this header nor RCCL
+// device_util.h   what all four share: HIP_CHECK, DevBuf / PinBuf (the one
+//                 owner of device and pinned memory), the device binary
+//                 search, ceil_log2, read_back, the iota and bounds kernels
+// cub_util.h      the hipCUB wrappers (engine.hip and coarsen.hip)
 // sweep_schedule.h holds the schedule's host arithmetic (no HIP).
 #ifndef MINIVITE_ENGINE_INTERNAL_H
 #define MINIVITE_ENGINE_INTERNAL_H
 
-#include <chrono>
 #include <condition_variable>
-#include <cstdio>
-#include <cstdlib>
 #include <mutex>
 #include <vector>
 
-#include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
 #include "../../include/minivite_hip.h"
+#include "device_util.h"
 #include "sweep_schedule.h"
-
-#define HIP_CHECK(x)                                                         \
-    do {                                                                      \
-        hipError_t _e = (x);                                                  \
-        if (_e != hipSuccess) {                                               \
-            std::fprintf(stderr, "HIP error %s at %s:%d: %s\n",               \
-                         hipGetErrorString(_e), __FILE__, __LINE__, #x);      \
-            std::abort();                                                     \
-        }                                                                     \
-    } while (0)
 
 #define NCCL_CHECK(x)                                                         \
     do {                                                                      \
@@ -44,8 +36,6 @@
             std::abort();                                                     \
         }                                                                     \
     } while (0)
-
-using i64 = int64_t;
 
 struct Cinfo {     // localCinfo / localCupdate entry (Comm, dspl.hpp:61-66)
     i64 size;
@@ -64,86 +54,10 @@ struct Info16 {    // wire record for cinfo replies / delta routing: the
 // indices are clamped non-negative).
 __device__ __forceinline__ i64 clamp0(i64 x) { return x > 0 ? x : 0; }
 
-__device__ __forceinline__ i64 dev_lower_bound(const i64 *a, i64 n, i64 key) {
-    i64 lo = 0, hi = n;
-    while (lo < hi) {
-        i64 mid = (lo + hi) >> 1;
-        if (a[mid] < key) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 __device__ __forceinline__ i64 dev_bsearch(const i64 *a, i64 n, i64 key) {
     i64 p = dev_lower_bound(a, n, key);
     return (p < n && a[p] == key) ? p : -1;
 }
-
-__device__ __forceinline__ void atomic_add_i64(i64 *p, i64 v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(p),
-              static_cast<unsigned long long>(v));
-}
-
-inline int grid_for(i64 n, int block = 256, int cap = 2048) {
-    i64 g = (n + block - 1) / block;
-    return (int)std::min<i64>(std::max<i64>(g, 1), cap);
-}
-
-using clk = std::chrono::steady_clock;
-inline double ms_since(clk::time_point t0) {
-    return std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-}
-
-// Move-only owner of one device (hipMalloc) or pinned host (hipHostMalloc)
-// allocation. reserve() is grow-only and does NOT preserve contents; it
-// floors n at one element so the pointer is never null once reserved.
-template <class T, bool PINNED = false> struct DevBuf {
-    T *ptr = nullptr;
-    i64 cap = 0; // elements
-    DevBuf() = default;
-    DevBuf(DevBuf &&o) noexcept : ptr(o.ptr), cap(o.cap) {
-        o.ptr = nullptr;
-        o.cap = 0;
-    }
-    DevBuf &operator=(DevBuf &&o) noexcept {
-        std::swap(ptr, o.ptr); // o's destructor frees what we held
-        std::swap(cap, o.cap);
-        return *this;
-    }
-    ~DevBuf() { release(); }
-    // true when it (re)allocated
-    bool reserve(i64 n) {
-        n = std::max<i64>(n, 1);
-        if (n <= cap) return false;
-        release();
-        if (PINNED)
-            HIP_CHECK(hipHostMalloc((void **)&ptr, sizeof(T) * n));
-        else
-            HIP_CHECK(hipMalloc((void **)&ptr, sizeof(T) * n));
-        cap = n;
-        return true;
-    }
-    void release() {
-        if (!ptr) return;
-        if (PINNED)
-            HIP_CHECK(hipHostFree(ptr));
-        else
-            HIP_CHECK(hipFree(ptr));
-        ptr = nullptr;
-        cap = 0;
-    }
-    // take over a device allocation of n >= 1 elements made elsewhere
-    // with hipMalloc (what was held is freed); the caller lets go of p
-    void adopt(T *p, i64 n) {
-        static_assert(!PINNED, "adopt() takes hipMalloc memory");
-        release();
-        ptr = p;
-        cap = n;
-    }
-    T *get() const { return ptr; }
-    operator T *() const { return ptr; }
-};
-template <class T> using PinBuf = DevBuf<T, true>;
 
 // one point-to-point message of a batched exchange (see exchange())
 struct Xfer {
@@ -199,7 +113,7 @@ struct mv_graph_state {
 
     // graph (device)
     i64 nv = 0, lnv = 0, lne = 0, base = 0, bound = 0;
-    int sort_bits = 64; // ceil(log2(nv)): radix sort width for id keys
+    int sort_bits = 64; // ceil_log2(nv): radix sort width for id keys
     std::vector<i64> parts_h;
     DevBuf<i64> d_parts;
     DevBuf<i64> d_xadj;
@@ -369,9 +283,22 @@ void comm_allreduce_host(mv_engine *e, double *vals, int n);
 // The last run's phase assignment as LABELS in original local order, in
 // e->d_res (device). Null before the first run.
 const i64 *phase_labels_device(mv_engine *e);
-// k_select_remote on st: appends every tail outside [base, bound) to d_out
-void select_remote(hipStream_t st, i64 lne, const i64 *d_tails, i64 base,
-                   i64 bound, i64 *d_out, unsigned long long *d_count);
+// The values of d_vals[0,n) outside [base, bound), sorted and distinct, in
+// d_ids (grown to fit, never null); returns their count. The values are
+// ids below 2^bits. Synchronises st.
+i64 remote_ids(hipStream_t st, i64 n, const i64 *d_vals, i64 base, i64 bound,
+               int bits, DevBuf<i64> &d_ids);
+// off[r+1] - off[r] = what rank r sends to `me`: column `me` of a count
+// matrix (allgather_counts). My own entry counts only where my segment
+// travels with the others.
+inline void recv_offsets(const std::vector<i64> &matrix, int p, int me,
+                         bool with_own, std::vector<i64> &off) {
+    off.assign(p + 1, 0);
+    for (int r = 0; r < p; r++)
+        off[r + 1] = off[r] + (r == me && !with_own
+                                   ? 0
+                                   : matrix[(size_t)r * p + me]);
+}
 
 // ---- sweep.hip: the K4 launches of mv_engine_run ----
 enum SweepIter1 { // the kernel of iteration 1

@@ -60,12 +60,6 @@ static void a2a64(mv_engine *e, const void *send, const i64 *soff, void *recv,
     alltoallv(e, send, soff, recv, roff, 8, ncclInt64, e->comm, e->stream);
 }
 
-static int id_bits(i64 nv) {
-    int b = 1;
-    while ((1ll << b) < nv) b++;
-    return b;
-}
-
 // d_vals[k] = the owner's table entry of d_uniq[k]: d_uniq holds sorted
 // distinct global ids of a level split by parts, d_table one value per
 // vertex this rank owns. Requests are bucketed by owner, counted, sent,
@@ -75,18 +69,14 @@ static void dist_fetch(mv_engine *e, const i64 *parts, const i64 *d_uniq,
     const int p = e->nranks, me = e->rank;
     hipStream_t st = e->stream;
     std::vector<uint64_t> keys(parts, parts + p + 1);
-    std::vector<i64> soff(p + 1), roff(p + 1, 0), cnt(p),
-        m((size_t)p * p);
+    std::vector<i64> soff(p + 1), roff, cnt(p), m((size_t)p * p);
     mv_lower_bounds(st, (const uint64_t *)d_uniq, nuniq, keys.data(), p + 1,
                     soff.data());
     for (int r = 0; r < p; r++) cnt[r] = soff[r + 1] - soff[r];
     gather_counts(e, cnt.data(), m.data());
-    for (int r = 0; r < p; r++)
-        roff[r + 1] = roff[r] + (r == me ? 0 : m[(size_t)r * p + me]);
+    recv_offsets(m, p, me, /*with_own*/ false, roff);
     const i64 nreq = roff[p];
-    DevBuf<i64> d_req, d_rep;
-    d_req.reserve(nreq);
-    d_rep.reserve(nreq);
+    DevBuf<i64> d_req(nreq), d_rep(nreq);
     a2a64(e, d_uniq, soff.data(), d_req, roff.data());
     mv_gather_owned(st, nreq, d_req, parts[me], d_table, d_rep);
     mv_gather_owned(st, cnt[me], d_uniq + soff[me], parts[me], d_table,
@@ -102,13 +92,11 @@ static void dist_lookup(mv_engine *e, const i64 *parts, i64 nv,
                         const i64 *d_ids, i64 n, const i64 *d_table,
                         i64 *d_out) {
     mv_unique_ids u;
-    mv_sort_unique_ids(e->stream, n, d_ids, id_bits(nv), &u);
-    DevBuf<i64> d_vals;
-    d_vals.reserve(u.nuniq);
+    mv_sort_unique_ids(e->stream, n, d_ids, ceil_log2(nv), &u);
+    DevBuf<i64> d_vals(u.nuniq);
     dist_fetch(e, parts, u.d_uniq, u.nuniq, d_table, d_vals);
     mv_scatter_unique(e->stream, &u, d_vals, d_out);
     HIP_CHECK(hipStreamSynchronize(e->stream));
-    mv_unique_ids_free(&u);
 }
 
 // this rank's slice of a coarse level, on the device
@@ -140,9 +128,8 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
     // a slice the caller already refused may not even have my parts entries
     // (built for fewer ranks): they are read only for a sound one
     const i64 base = bad ? 0 : parts[me], bound = bad ? 0 : parts[me + 1];
-    const int bits = id_bits(nv);
-    std::vector<i64> soff(p + 1, 0), roff(p + 1, 0), cnt(p),
-        m((size_t)p * p);
+    const int bits = ceil_log2(nv);
+    std::vector<i64> soff(p + 1, 0), roff, cnt(p), m((size_t)p * p);
     std::vector<uint64_t> keys(p + 1);
 
     // ---- (a) renumber: distinct labels to their owners ----
@@ -155,16 +142,11 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
     }
     mv_unique_ids u;
     if (!bad) {
-        DevBuf<i64> d_lab;
-        DevBuf<unsigned> d_err;
-        d_lab.reserve(lnv);
-        d_err.reserve(1);
+        DevBuf<i64> d_lab(lnv);
+        DevBuf<unsigned> d_err(1);
         HIP_CHECK(hipMemsetAsync(d_err, 0, 4, st));
         mv_check_labels(st, lnv, d_labels, nv, d_lab, d_err);
-        unsigned h_err = 0;
-        HIP_CHECK(hipMemcpyAsync(&h_err, d_err, 4, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        if (h_err) {
+        if (read_back(d_err.get(), st)) {
             std::fprintf(stderr,
                          "coarsen (rank %d): community label outside "
                          "[0, nv=%lld)\n",
@@ -173,38 +155,28 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
         } else {
             mv_sort_unique_ids(st, lnv, d_lab, bits, &u);
             for (int r = 0; r <= p; r++) keys[r] = (uint64_t)parts[r];
-            mv_lower_bounds(st, (const uint64_t *)u.d_uniq, u.nuniq,
+            mv_lower_bounds(st, (const uint64_t *)u.d_uniq.get(), u.nuniq,
                             keys.data(), p + 1, soff.data());
         }
     }
     for (int r = 0; r < p; r++) cnt[r] = bad ? -1 : soff[r + 1] - soff[r];
     gather_counts(e, cnt.data(), m.data());
     for (size_t k = 0; k < m.size(); k++)
-        if (m[k] < 0) { // some rank refused: everyone does, before any send
-            mv_unique_ids_free(&u);
+        if (m[k] < 0) // some rank refused: everyone does, before any send
             return -1;
-        }
-    for (int r = 0; r < p; r++)
-        roff[r + 1] = roff[r] + (r == me ? 0 : m[(size_t)r * p + me]);
+    recv_offsets(m, p, me, /*with_own*/ false, roff);
     i64 nc = 0, offset = 0;
     DevBuf<i64> d_dense; // dense coarse id of every owned label in use
     {
         const i64 nreq = roff[p];
-        DevBuf<i64> d_req;
-        DevBuf<unsigned> d_used, d_rank;
-        d_req.reserve(nreq);
-        d_used.reserve(lnv + 1);
-        d_rank.reserve(lnv + 1);
+        DevBuf<i64> d_req(nreq);
+        DevBuf<unsigned> d_used(lnv + 1), d_rank(lnv + 1);
         a2a64(e, u.d_uniq, soff.data(), d_req, roff.data());
         HIP_CHECK(hipMemsetAsync(d_used, 0, 4 * (lnv + 1), st));
         mv_mark_owned(st, nreq, d_req, base, d_used);
         mv_mark_owned(st, cnt[me], u.d_uniq + soff[me], base, d_used);
         mv_exclusive_sum_u32(st, d_used, d_rank, lnv + 1);
-        unsigned h_cnt = 0;
-        HIP_CHECK(hipMemcpyAsync(&h_cnt, d_rank + lnv, 4,
-                                 hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        std::vector<i64> mine(p, (i64)h_cnt);
+        std::vector<i64> mine(p, (i64)read_back(d_rank + lnv, st));
         gather_counts(e, mine.data(), m.data());
         for (int r = 0; r < p; r++) {
             if (r < me) offset += m[(size_t)r * p];
@@ -216,50 +188,31 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
     }
     out->d_map.reserve(lnv);
     {
-        DevBuf<i64> d_vals;
-        d_vals.reserve(u.nuniq);
+        DevBuf<i64> d_vals(u.nuniq);
         dist_fetch(e, parts, u.d_uniq, u.nuniq, d_dense, d_vals);
         mv_scatter_unique(st, &u, d_vals, out->d_map);
         HIP_CHECK(hipStreamSynchronize(st));
     }
-    mv_unique_ids_free(&u);
     out->nc = nc;
     out->parts.resize(p + 1);
     for (int r = 0; r <= p; r++) out->parts[r] = (nc * r) / p;
     out->lnc = out->parts[me + 1] - out->parts[me];
     if (stop_if_identity && nc == nv) return 0;
 
-    // ---- (b) coarse ids of the tails: remote ones are fetched ----
-    mv_unique_ids gh;
-    DevBuf<i64> d_gmap;
-    {
-        DevBuf<i64> d_rem;
-        DevBuf<unsigned long long> d_nrem;
-        d_rem.reserve(lne);
-        d_nrem.reserve(1);
-        HIP_CHECK(hipMemsetAsync(d_nrem, 0, 8, st));
-        select_remote(st, lne, d_tails, base, bound, d_rem, d_nrem);
-        unsigned long long nrem = 0;
-        HIP_CHECK(hipMemcpyAsync(&nrem, d_nrem, 8, hipMemcpyDeviceToHost, st));
-        HIP_CHECK(hipStreamSynchronize(st));
-        mv_sort_unique_ids(st, (i64)nrem, d_rem, bits, &gh);
-    }
-    d_gmap.reserve(gh.nuniq);
-    dist_fetch(e, parts, gh.d_uniq, gh.nuniq, out->d_map, d_gmap);
-
-    // ---- keys, local sort + run reduction: one partial per local pair ----
-    int shift = 1;
-    while ((1ll << shift) < nc) shift++;
+    // ---- (b) coarse ids of the tails: remote ones are fetched; then the
+    // keys, local sort + run reduction: one partial per local pair ----
+    const int shift = ceil_log2(nc);
     mv_key_runs part;
     {
-        DevBuf<uint64_t> d_keys;
-        d_keys.reserve(lne);
+        DevBuf<i64> d_gids; // the distinct remote tails, sorted
+        const i64 ngh = remote_ids(st, lne, d_tails, base, bound, bits, d_gids);
+        DevBuf<i64> d_gmap(ngh);
+        dist_fetch(e, parts, d_gids, ngh, out->d_map, d_gmap);
+        DevBuf<uint64_t> d_keys(lne);
         mv_coarse_keys_dist(st, lnv, lne, d_xadj, d_tails, base, bound,
-                            out->d_map, gh.d_uniq, gh.nuniq, d_gmap, shift,
-                            d_keys);
+                            out->d_map, d_gids, ngh, d_gmap, shift, d_keys);
         mv_sort_reduce_keys(st, lne, d_keys, d_w, 2 * shift, &part);
     }
-    mv_unique_ids_free(&gh);
 
     // ---- redistribution: every partial to the owner of its row ----
     for (int r = 0; r <= p; r++)
@@ -275,20 +228,17 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
                          "coarsen (rank %d): rank %d would receive %lld "
                          "partial edges, need < 2^31 - 1\n",
                          me, q, (long long)tot);
-            mv_key_runs_free(&part);
             return -1;
         }
     }
     // segments by ascending sender, my own in its place: the stable sort
     // then adds the per-rank partials of a pair in rank order
-    for (int r = 0; r < p; r++) roff[r + 1] = roff[r] + m[(size_t)r * p + me];
+    recv_offsets(m, p, me, /*with_own*/ true, roff);
     const i64 nrecv = roff[p];
     mv_key_runs fin;
     {
-        DevBuf<uint64_t> d_rk;
-        DevBuf<double> d_rw;
-        d_rk.reserve(nrecv);
-        d_rw.reserve(nrecv);
+        DevBuf<uint64_t> d_rk(nrecv);
+        DevBuf<double> d_rw(nrecv);
         if (cnt[me] > 0) {
             HIP_CHECK(hipMemcpyAsync(d_rk + roff[me], part.d_key + soff[me],
                                      8 * cnt[me], hipMemcpyDeviceToDevice,
@@ -302,17 +252,13 @@ static int coarsen_dist_device(mv_engine *e, const i64 *parts, i64 nv,
         // ---- owner: stable sort of the segments, run reduction ----
         mv_sort_reduce_keys(st, nrecv, d_rk, d_rw, 2 * shift, &fin);
     }
-    mv_key_runs_free(&part);
     out->ne = fin.n;
     out->d_xadj.reserve(out->lnc + 1);
     out->d_tails.reserve(fin.n);
     mv_coarse_rows(st, out->parts[me], out->lnc, fin.n, shift, fin.d_key,
                    out->d_xadj, out->d_tails);
     HIP_CHECK(hipStreamSynchronize(st));
-    // the run weights ARE the coarse weights (never fewer than 1 element)
-    out->d_w.adopt(fin.d_w, std::max<i64>(fin.n, 1));
-    fin.d_w = nullptr;
-    mv_key_runs_free(&fin);
+    out->d_w = std::move(fin.d_w); // the run weights ARE the coarse weights
     return 0;
 }
 
@@ -428,28 +374,22 @@ static mv_hierarchy *run_phases(mv_engine *e, const mv_graph *g, double lower,
                                   e->d_tails,
                                   e->unit_weights ? nullptr : e->d_ew.get(),
                                   phase_labels_device(e),
-                                  /*stop_if_identity*/ true, &c) != 0) {
-                mv_coarse_dev_free(&c);
+                                  /*stop_if_identity*/ true, &c) != 0)
                 return nullptr;
-            }
-            if (c.nc == e->lnv) { // no merge: the hierarchy is complete
-                mv_coarse_dev_free(&c);
-                break;
-            }
+            if (c.nc == e->lnv) break; // no merge: the hierarchy is complete
             const double dev_ms = ms_since(t0); // the kernels, synchronised
             map.resize(e->lnv);
             std::vector<i64> cx(c.nc + 1), ct(c.ne);
             std::vector<double> cw(c.ne);
-            to_host(map, c.d_map);
-            to_host(cx, c.d_xadj);
-            to_host(ct, c.d_tails);
-            to_host(cw, c.d_w);
+            to_host(map, c.d_map.get());
+            to_host(cx, c.d_xadj.get());
+            to_host(ct, c.d_tails.get());
+            to_host(cw, c.d_w.get());
             const double copy_ms = ms_since(t0) - dev_ms;
             const i64 parts[2] = {0, c.nc};
             nc = c.nc;
             ng = mv_graph_from_csr(c.nc, 0, 1, parts, c.nc, c.ne, cx.data(),
                                    ct.data(), cw.data());
-            mv_coarse_dev_free(&c);
             info.coarsen_ms = ms_since(t0);
             if (getenv("MV_COARSEN_DEBUG"))
                 std::fprintf(stderr,
